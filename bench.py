@@ -17,7 +17,11 @@ collective costs about as much host and link latency as a whole forward);
 ``--shard candidates`` gives every rank its own 128 candidates on all 16 rows and
 all-gathers the per-candidate values instead.
 
-Prints one JSON line (rank 0): value = KG-evals/s over all ranks, plus
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON line (rank 0): value =
+KG-evals/s over all ranks, ``ms_per_step`` = the milliseconds one timed step took.  ``--dump-outputs DIR``
+also writes the last timed step's per-candidate KG values, as the exchange leaves them, to ``DIR/kg.npy``
+(float64; the inputs are seeded, so two runs with the same arguments write the same inputs' values).
+Everything else is measured only under ``--full`` (``null`` in a plain line):
   * ``roofline``: the dominant kernel's duration (HIP events on its launch
     stream) against the fp64 roof (78.6 TF/s, vector = matrix on MI355X): ``achieved``
     = SURVEY 8(d)'s counted flops per launch / duration, ``frac`` = achieved / peak;
@@ -45,6 +49,7 @@ for _p in (REPO, os.path.join(REPO, "decoupled-kg_amd")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
@@ -117,7 +122,44 @@ def parse():
                          "KG-evals/s; profiles/r05/stress_streams/)")
     ap.add_argument("--stress-steps", type=int, default=16,
                     help="timed forwards of the stress leg (BASELINE configs[4] shape, fp64; 0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also run every other leg (single-stream run, per-kernel "
+                         "rooflines, batch diagnostics, value+gradient, B = 1 latency, state preparation, "
+                         "non-degenerate, stress and stress32 legs, the one-rank RCCL exchange, the CPU baseline); "
+                         "without it the line holds the headline's figures and null for the rest")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step handed its caller as DIR/<name>.npy "
+                         "(kg.npy: the per-candidate KG values, float64)")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, print the line; every leg with a run of its own is off
+        args.cpu_seconds = 0.0
+        args.grad_steps = args.b1_calls = args.prep_reps = 0
+        args.nd_steps = args.stress_steps = args.stress32_steps = 0
+        args.single_rank_pg = 0
+    return args
+
+
+def last_step_outputs(tp, steps):
+    """What the timed path handed its caller for its last step: the per-candidate KG values of step
+    ``steps - 1`` after the exchange (world 1: the forward's own row; scalarisations sharded: the mean over
+    every rank's weight rows, [B]; candidates sharded: every rank's candidates, [world, B])."""
+    x = tp.xchg
+    slot, r = x._slot(steps - 1)
+    if x.mode == "gather":
+        rows = x.rows[slot]
+        kg = x.gathered[slot][:x.world * rows * x.B].view(x.world, rows, x.B)[:, r]
+    else:
+        kg = x.bufs[slot][r]
+        if x.collective:  # the buffer holds the sum over ranks of S_local * (the rank's mean)
+            kg = kg / (x.S_local * x.world)
+    return {"kg": kg.detach().to("cpu", torch.double).contiguous()}
+
+
+def dump_outputs(outdir, arrays):
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(outdir, f"{name}.npy"), t.numpy())
 
 
 def stage_model(w, m, n, N, B, S, d):
@@ -253,6 +295,7 @@ class Throughput:
         self.head = 0
         self.launch_threads = -1
         self.skew = 0
+        self.want_breakdown = False  # --full: one more, untimed, replay of a one-period region with event marks
 
     def chunks(self, k0, k1, G):
         """(first step, batches, unit index in its period) of the launches covering steps k0 .. k1 - 1:
@@ -428,7 +471,7 @@ class Throughput:
             launcher.arm(0.0)
             launcher.close()
         self.breakdown = None
-        if graphs and graph == 2 and launcher is None and steps == E:
+        if self.want_breakdown and graphs and graph == 2 and launcher is None and steps == E:
             # where a one-period region's time goes: the same launches again, untimed, with an event on every
             # stream after each of its pieces and the host clock after each hipGraphLaunch; GPU times relative
             # to an event on the main stream just before the first launch
@@ -589,15 +632,18 @@ def main():
         tp.head = args.graph_head
         tp.launch_threads = args.launch_threads
         tp.skew = args.stream_skew
+        tp.want_breakdown = args.full
         return w, model, D, X0, W, acq, tp
 
     w, model, D, X0, W, acq, tp = setup(args.workload)
     single = None
-    if args.streams > 1 or args.graph:
+    if args.full and (args.streams > 1 or args.graph):
         e1 = tp.run(1, args.steps, args.warmup, False, world, G=1)
         single = {"value": world * w.B * args.steps / e1, "ms_per_step": e1 / args.steps * 1e3}
     elapsed = tp.run(max(1, args.streams), args.steps, args.warmup, args.graph, world)
     value = world * w.B * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs(tp, args.steps))
     mine = torch.tensor([tp.compute_ms, tp.exposed_ms, elapsed * 1e3], dtype=torch.double, device=dev)
     if world > 1:
         allr = [torch.zeros_like(mine) for _ in range(world)]
@@ -610,30 +656,32 @@ def main():
                         "exposed: from there to the end of the final exchange (the collective nothing overlaps); "
                         "batch_stats: each rank's own pairs (its weight rows x its candidates)"}
 
-    # ---- per-kernel rooflines; the dominant kernel's is the line's `roofline`
-    pmc = {}
-    pmc_path = pmc_file(args)
-    if os.path.exists(pmc_path):
-        try:
-            pmc = json.load(open(pmc_path))
-        except (OSError, ValueError):
-            pmc = {}
-    # the stages as the timed region launches them: G batches per launch
-    G = tp.G
-    model_fb = stage_model(w, w.m, [mm.num_train for mm in model.models], D.shape[0], G * w.B, w.S, w.d)
-    gplan_roof = acq._state.plan(acq._W, acq._target, G * w.B, f32=args.precision == "fp32")
-    stages = stage_rooflines(gplan_roof, tp.XG, model_fb, args.profile_reps, args.precision, pmc, G=G, B=w.B)
-    del gplan_roof
-    dom = max(stages, key=lambda k: stages[k]["avg_launch_us"])
-    roof = dict(stages[dom], kernel=dom,
-                bound_note="fp64 compute roof: 78.6 TF/s is both the vector and the matrix fp64 peak of MI355X; "
-                           "achieved = SURVEY 8(d) counted flops per launch / launch duration; the envelope is "
-                           "VALU-issue and latency bound (its comparisons, selects and reductions are not counted "
-                           "flops): valu_busy_frac is its occupancy figure",
-                stages={k: {kk: v[kk] for kk in ("avg_launch_us", "bound", "frac", "valu_busy_frac", "traffic")}
-                        for k, v in stages.items()},
-                launch=f"{G} forward batch(es) of {w.B} candidates per launch, as in the timed region",
-                pmc_source=os.path.relpath(pmc_path, REPO) if pmc else None)
+    # ---- --full: per-kernel rooflines; the dominant kernel's is the line's `roofline`
+    roof = None
+    if args.full:
+        pmc = {}
+        pmc_path = pmc_file(args)
+        if os.path.exists(pmc_path):
+            try:
+                pmc = json.load(open(pmc_path))
+            except (OSError, ValueError):
+                pmc = {}
+        # the stages as the timed region launches them: G batches per launch
+        G = tp.G
+        model_fb = stage_model(w, w.m, [mm.num_train for mm in model.models], D.shape[0], G * w.B, w.S, w.d)
+        gplan_roof = acq._state.plan(acq._W, acq._target, G * w.B, f32=args.precision == "fp32")
+        stages = stage_rooflines(gplan_roof, tp.XG, model_fb, args.profile_reps, args.precision, pmc, G=G, B=w.B)
+        del gplan_roof
+        dom = max(stages, key=lambda k: stages[k]["avg_launch_us"])
+        roof = dict(stages[dom], kernel=dom,
+                    bound_note="fp64 compute roof: 78.6 TF/s is both the vector and the matrix fp64 peak of MI355X; "
+                               "achieved = SURVEY 8(d) counted flops per launch / launch duration; the envelope is "
+                               "VALU-issue and latency bound (its comparisons, selects and reductions are not counted "
+                               "flops): valu_busy_frac is its occupancy figure",
+                    stages={k: {kk: v[kk] for kk in ("avg_launch_us", "bound", "frac", "valu_busy_frac", "traffic")}
+                            for k, v in stages.items()},
+                    launch=f"{G} forward batch(es) of {w.B} candidates per launch, as in the timed region",
+                    pmc_source=os.path.relpath(pmc_path, REPO) if pmc else None)
 
     # ---- whole-forward roofline as BASELINE.md defines it: max(F/P, Bytes/BW) / T_measured
     f_fwd, b_fwd = survey_model(w.m, [mm.num_train for mm in model.models], D.shape[0], w.S, w.B, w.d)
@@ -641,19 +689,22 @@ def main():
     t_min = max(f_fwd / (FP64_PEAK_TFLOPS * 1e12), b_fwd / (HBM_PEAK_GBS * 1e9))
     fwd_roof = {"definition": "BASELINE.md: max(F/P_fp64, Bytes/BW_HBM) / T_forward", "flops": f_fwd,
                 "bytes": b_fwd, "t_min_us": t_min * 1e6, "t_forward_us": t_fwd * 1e6, "frac": t_min / t_fwd}
-    stats = batch_stats(tp.plan, tp.Xd)
-    # every rank's pair mix (the work a weak-scaling rank does depends on how many of its pairs walk an envelope)
-    mine_st = torch.tensor([stats["zero_kg_frac"], stats["short_circuit_frac"], stats["envelope_lines_mean"],
-                            (1.0 - stats["zero_kg_frac"]) * stats["pairs"]], dtype=torch.double, device=dev)
-    if world > 1:
-        all_st = [torch.zeros_like(mine_st) for _ in range(world)]
-        dist.all_gather(all_st, mine_st)
-    else:
-        all_st = [mine_st]
-    per_rank["batch_stats"] = {"zero_kg_frac": [float(r[0]) for r in all_st],
-                               "short_circuit_frac": [float(r[1]) for r in all_st],
-                               "envelope_lines_mean": [float(r[2]) for r in all_st],
-                               "pairs_with_kg_above_0": [int(round(float(r[3]))) for r in all_st]}
+    # ---- --full: the batch's diagnostics (one forward_stats launch)
+    stats = None
+    if args.full:
+        stats = batch_stats(tp.plan, tp.Xd)
+        # every rank's pair mix (the work a weak-scaling rank does depends on how many of its pairs walk an envelope)
+        mine_st = torch.tensor([stats["zero_kg_frac"], stats["short_circuit_frac"], stats["envelope_lines_mean"],
+                                (1.0 - stats["zero_kg_frac"]) * stats["pairs"]], dtype=torch.double, device=dev)
+        if world > 1:
+            all_st = [torch.zeros_like(mine_st) for _ in range(world)]
+            dist.all_gather(all_st, mine_st)
+        else:
+            all_st = [mine_st]
+        per_rank["batch_stats"] = {"zero_kg_frac": [float(r[0]) for r in all_st],
+                                   "short_circuit_frac": [float(r[1]) for r in all_st],
+                                   "envelope_lines_mean": [float(r[2]) for r in all_st],
+                                   "pairs_with_kg_above_0": [int(round(float(r[3]))) for r in all_st]}
 
     # ---- value + gradient (dkg_plan_forward_grad: the optimize_acqf L-BFGS-B path), same batch
     grad_info = None

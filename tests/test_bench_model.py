@@ -72,3 +72,46 @@ def test_batches_per_launch_divides_the_period(monkeypatch):
         a = b.parse()
         g = b.batches_per_launch(E, a)
         assert g == want and E % g == 0
+
+
+def test_plain_run_switches_every_other_leg_off(monkeypatch):
+    """Without --full only the headline's timed steps run: every leg with a run of its own is off; --full
+    leaves the legs' defaults as they were."""
+    b = _bench()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = b.parse()
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (20, 5)
+    assert (a.cpu_seconds, a.grad_steps, a.b1_calls, a.prep_reps, a.nd_steps, a.stress_steps, a.stress32_steps,
+            a.single_rank_pg) == (0, 0, 0, 0, 0, 0, 0, 0)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.full and a.dump_outputs == "d"
+    assert (a.cpu_seconds, a.grad_steps, a.b1_calls, a.prep_reps, a.nd_steps, a.stress_steps, a.stress32_steps,
+            a.single_rank_pg) == (12.0, 50, 200, 5, 256, 16, 16, 1)
+
+
+def test_dump_outputs_writes_the_last_steps_row(tmp_path):
+    """--dump-outputs: the row of the last timed step out of the exchange's buffers (a partial last period
+    included), written as float64 kg.npy."""
+    import numpy as np
+    import torch
+
+    from dkg_amd.dist import BatchExchange
+
+    b = _bench()
+
+    class TP:
+        pass
+
+    for mode, shape in (("reduce", (3,)), ("gather", (1, 3))):
+        tp = TP()
+        tp.xchg = BatchExchange(3, 4, mode, S_local=2, device="cpu")
+        for k in range(6):
+            tp.xchg.block(k, 1).copy_(torch.arange(3, dtype=torch.double) + 10 * k)
+            tp.xchg.done(k)
+        tp.xchg.flush(6)
+        out = b.last_step_outputs(tp, 6)
+        assert out["kg"].shape == shape and out["kg"].reshape(-1).tolist() == [50.0, 51.0, 52.0]
+        b.dump_outputs(str(tmp_path / mode), out)
+        got = np.load(str(tmp_path / mode / "kg.npy"))
+        assert got.dtype == np.float64 and got.shape == shape and got.reshape(-1).tolist() == [50.0, 51.0, 52.0]

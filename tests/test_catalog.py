@@ -11,7 +11,8 @@ import torch
 from dkg_amd.catalog import DataCatalog
 from dkg_amd.model import ModelListGPState, SingleTaskGPState, from_state_dict, to_state_dict
 
-REF_DATA = "/root/reference/data"
+# the reference's data layout (shared/gp-problem/<name>.pt) with its lengthscales/0 problem file, kept as a fixture
+REF_DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _model():
@@ -129,7 +130,6 @@ def test_unsafe_archive_is_refused(tmp_path):
         c.uncompress_checkpoints("k")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference data not present")
 def test_reads_the_reference_shared_gp_problem():
     """The reference's own shared GP problem file, read with weights_only=True (nothing executed)."""
     prob = DataCatalog.load_shared_gp_test_problem_data("lengthscales/0", data_dir=REF_DATA)

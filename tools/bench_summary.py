@@ -8,7 +8,7 @@ for f in sys.argv[1:]:
     nd = d.get("nondegenerate") or {}
     st = d.get("stress") or {}
     b1 = d.get("latency_b1") or {}
-    r = d["roofline"]
+    r = d.get("roofline") or {"stages": {}, "kernel": None, "frac": 0.0}  # null without bench.py --full
     print(f, {"M/s": round(d["value"] / 1e6, 2), "us/step": round(d["ms_per_step"] * 1e3, 2),
               "single_us": round((d.get("single_stream") or {}).get("ms_per_step", 0) * 1e3, 2),
               "nd M/s": round(nd.get("value", 0) / 1e6, 2), "nd env us": round(nd.get("envelope_us", 0), 1),

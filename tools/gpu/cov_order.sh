@@ -6,7 +6,7 @@ set -uo pipefail
 out=${1:-gpurun_out/co}
 mkdir -p "$out"
 export TMPDIR=/tmp
-B="python3 bench.py --steps 20 --warmup 2 --cpu-seconds 0 --profile-reps 2 --grad-steps 0 --b1-calls 0 --nd-steps 0 --stress-steps 0 --stress32-steps 0 --streams 1 --graph 0"
+B="python3 bench.py --full --steps 20 --warmup 2 --cpu-seconds 0 --profile-reps 2 --grad-steps 0 --b1-calls 0 --nd-steps 0 --stress-steps 0 --stress32-steps 0 --streams 1 --graph 0"
 for wl in ${WLS:-stress headline}; do
   g=10; [ "$wl" = stress ] && g=1
   for o in ${ORDERS:-0 1 2}; do

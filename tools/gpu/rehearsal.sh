@@ -6,7 +6,7 @@ out=${1:-gpurun_out/reh}
 mkdir -p "$out"
 for shard in scalarisations candidates; do
   DKG_BENCH_BACKEND=gloo timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 2 --steps 20 --warmup 5 --shard $shard \
+    --master-addr 127.0.0.1 --master-port 29512 bench.py --full --gpus 2 --steps 20 --warmup 5 --shard $shard \
     > "$out/gloo2_$shard.json" 2> "$out/gloo2_$shard.err" || { tail -20 "$out/gloo2_$shard.err"; exit 1; }
   python3 tools/bench_summary.py "$out/gloo2_$shard.json"
 done

@@ -5,7 +5,7 @@ set -uo pipefail
 out=${1:-gpurun_out/tb}; shift || true
 mkdir -p "$out"
 export TMPDIR=/tmp
-timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- python3 bench.py ${*:---steps 20 --warmup 5} > "$out/bench.json" 2> "$out/bench.err" || { tail -5 "$out/bench.err"; exit 1; }
+timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- python3 bench.py --full ${*:---steps 20 --warmup 5} > "$out/bench.json" 2> "$out/bench.err" || { tail -5 "$out/bench.err"; exit 1; }
 f=$(find "$out/trace" -name "*kernel_stats.csv" | head -1)
 cp "$f" "$out/kernel_stats.csv"
 python3 - "$f" <<'PY'
