@@ -515,6 +515,61 @@ int dkg_cross_root(const dkg_output* o, int d, const double* x, int rows, double
   return hip_check(launch_cross_root(ca, (hipStream_t)stream), "cross_root_kernel");
 }
 
+size_t dkg_append_workspace(int n, int N) {
+  if (n < 1 || N < 0) return 0;
+  return APPEND_WS_BYTES;  // the info flag, lambda, l and beta' (1024 entries each)
+}
+
+int dkg_append_observation(const dkg_output* o, int d, const double* L, const double* Linv, const double* disc, int N,
+                           const double* train_x, const double* train_y, double jitter, double* L_new,
+                           double* Linv_new, double* alpha_new, double* root_frag_new, double* disc_frag_new,
+                           double* disc_mean_new, void* work, size_t work_bytes, void* stream) {
+  if (!o || !L || !Linv || !train_x || !train_y || !L_new || !Linv_new || !alpha_new || !root_frag_new || !work ||
+      !o->inv_lengthscale)
+    return fail(DKG_ERR_ARG, "NULL pointer");
+  if (N < 0) return fail(DKG_ERR_ARG, "N=%d discretisation points", N);
+  if (N > 0 && (!disc || !o->disc_frag || !disc_frag_new || !disc_mean_new)) return fail(DKG_ERR_ARG, "NULL pointer");
+  const int n = o->n;
+  if (n < 1) return fail(DKG_ERR_ARG, "n=%d training points", n);
+  if (pad16(n + 1) > 1024) return fail(DKG_ERR_UNSUPPORTED, "n=%d > 1024 training points", n + 1);
+  if (d < 1 || d > DKG_MAX_DIM) return fail(DKG_ERR_UNSUPPORTED, "d=%d (supported 1..%d)", d, DKG_MAX_DIM);
+  if (N > (1 << 22)) return fail(DKG_ERR_UNSUPPORTED, "N=%d discretisation points (supported <= %d)", N, 1 << 22);
+  if (o->kernel < DKG_MATERN12 || o->kernel > DKG_RBF) return fail(DKG_ERR_ARG, "kernel id %d", o->kernel);
+  if (!(jitter >= 0.0)) return fail(DKG_ERR_ARG, "jitter=%g", jitter);
+  if (work_bytes < dkg_append_workspace(n, N))
+    return fail(DKG_ERR_WORKSPACE, "workspace %zu bytes < required %zu", work_bytes, dkg_append_workspace(n, N));
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(work);
+  AppendArgs a{};
+  a.o = *o;
+  a.d = d;
+  a.N = N;
+  a.L = L;
+  a.M = Linv;
+  a.xt = train_x;
+  a.y = train_y;
+  a.diag = o->noise + jitter;  // as the old factorisation's kernel matrix took it
+  a.disc = disc;
+  a.Ln = L_new;
+  a.Mn = Linv_new;
+  a.alpha = alpha_new;
+  a.qn = disc_frag_new;
+  a.mean = disc_mean_new;
+  a.info = reinterpret_cast<int*>(ws);
+  a.lam = reinterpret_cast<double*>(ws + APPEND_WS_LAM);
+  a.lvec = reinterpret_cast<double*>(ws + APPEND_WS_L);
+  a.beta = reinterpret_cast<double*>(ws + APPEND_WS_BETA);
+  int st, h_info = 1;
+  if ((st = hip_check(hipMemsetAsync(a.info, 0, sizeof(int), s), "hipMemsetAsync")) ||
+      (st = hip_check(launch_append(a, root_frag_new, s), "append")) ||
+      (st = hip_check(hipMemcpyAsync(&h_info, a.info, sizeof(int), hipMemcpyDeviceToHost, s), "hipMemcpyAsync")) ||
+      (st = hip_check(hipStreamSynchronize(s), "hipStreamSynchronize")))
+    return st;
+  if (h_info != 0)
+    return fail(DKG_ERR_NOT_PD, "covariance not positive definite with the appended observation (pivot %d)", h_info);
+  return DKG_OK;
+}
+
 size_t dkg_forward_workspace(const dkg_output* outs, int m, int N, int B, int S) {
   if (!outs || m < 1 || m > DKG_MAX_OUTPUTS) return 0;
   return layout(outs, m, N, B, S).total + plan_slot_bytes() + 256;

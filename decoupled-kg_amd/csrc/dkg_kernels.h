@@ -141,6 +141,27 @@ hipError_t launch_tri_inverse(double* L, double* X, int n, const int* info, hipS
 hipError_t launch_alpha(const double* X, const double* y, double c, int n, double* alpha, const int* info,
                         hipStream_t s);
 hipError_t launch_pack_linv(const double* X, int n, double* rf, hipStream_t s);
+// One observation appended to an output's state (dkg_append.hip, dkg_append_observation).
+struct AppendArgs {
+  dkg_output o;            // the old output: n, kernel, hyperparameters, inv_lengthscale, disc_frag
+  int d, N;
+  const double* L;         // old L, row-major n x n
+  const double* M;         // old L^{-1}, row-major n x n
+  const double* xt;        // new train_x, (n + 1) x d, its last row the new point
+  const double* y;         // new targets, n + 1
+  double diag;             // noise + the old factorisation's jitter
+  const double* disc;      // [N x d]
+  double *Ln, *Mn;         // new L and L^{-1}, (n + 1) x (n + 1)
+  double* alpha;           // [pad16(n + 1)]
+  double* qn;              // new disc_frag, N_pad x pad16(n + 1)
+  double* mean;            // new disc_mean [pad16(N)]
+  double *lvec, *beta;     // workspace [1024] each: l and beta', zero padded
+  double* lam;             // workspace: lambda
+  int* info;               // workspace: 0, or n + 1 when lambda^2 <= 0
+};
+constexpr size_t APPEND_WS_LAM = 64, APPEND_WS_L = 256, APPEND_WS_BETA = 256 + 8192, APPEND_WS_BYTES = 256 + 16384;
+// The copy, solve, pack and discretisation launches of one append (root_frag: the new R^T, from Mn).
+hipError_t launch_append(const AppendArgs& a, double* root_frag, hipStream_t s);
 // fp32 quad-packed copy (frag32_index) of a pair-packed fp64 (rows x n) matrix.
 hipError_t launch_frag_to_f32(const double* frag, int rows, int n, float* out, hipStream_t s);
 // The plan's per-scalarisation intercepts and their maxima (Plan::icpt / itop / itopk), from mu_all.

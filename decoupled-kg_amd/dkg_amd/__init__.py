@@ -16,7 +16,7 @@ from .discretekg import (
     t_batch_mode_transform,
 )
 from .errors import BotorchTensorDimensionError, DkgNativeError, UnsupportedError
-from .gp_state import DeviceGPState
+from .gp_state import DeviceGPState, reset_state_stats, set_incremental_state, state_stats
 from .model import ModelListGPState, SingleTaskGPState, from_botorch, from_state_dict
 from .utils import is_power_of_2, make_torch_std_grid, sample_simplex
 
@@ -34,6 +34,9 @@ __all__ = [
     "DkgNativeError",
     "UnsupportedError",
     "DeviceGPState",
+    "set_incremental_state",
+    "state_stats",
+    "reset_state_stats",
     "ModelListGPState",
     "SingleTaskGPState",
     "from_botorch",

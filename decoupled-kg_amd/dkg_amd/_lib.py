@@ -17,7 +17,7 @@ from .errors import BotorchTensorDimensionError, DkgNativeError, NotPSDError, Un
 LIB_PATH = os.environ.get("DKG_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "_native",
                                                      "libdkg.so")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 DKG_XARG_MAX = 64  # include/dkg.h: largest B * d of dkg_plan_forward_grad_hostx
 DKG_PLAN_GRAD = 1
 DKG_PLAN_FORCE_WALK = 2  # test hook: envelope overflow path for every pair
@@ -68,6 +68,10 @@ SIGNATURES = {
                                     POINTER(c_void_p), POINTER(c_size_t), POINTER(c_void_p), POINTER(c_void_p),
                                     POINTER(c_double), c_void_p]),
     "dkg_cross_root": (c_int, [POINTER(DkgOutput), c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "dkg_append_workspace": (c_size_t, [c_int, c_int]),
+    "dkg_append_observation": (c_int, [POINTER(DkgOutput), c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                       c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_size_t, c_void_p]),
     "dkg_forward_workspace": (c_size_t, [POINTER(DkgOutput), c_int, c_int, c_int, c_int]),
     "dkg_forward": (c_int, [POINTER(DkgOutput), c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                             c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -40,7 +40,7 @@ import torch
 from torch import Tensor
 
 from .catalog import DataCatalog
-from .gp_state import DeviceGPState
+from .gp_state import DeviceGPState, set_incremental_state
 from .model import ModelListGPState, SingleTaskGPState, to_state_dict
 from .optim import DiscreteKgOptimisationSpec, draw_sobol_samples
 from .utils import sample_simplex
@@ -123,16 +123,31 @@ def run_mobo(problem: GPProblem, hyper: Dict[str, Sequence[float]], separate: bo
              n_init: int = 6, costs: Sequence[float] = (1, 10), n_scalarisations: int = 16,
              spec: Optional[DiscreteKgOptimisationSpec] = None, seed: int = 0,
              catalog: Optional[DataCatalog] = None, run_key: Optional[str] = None,
-             fit_hyperparams: str = "never") -> Dict[str, List]:
+             fit_hyperparams: str = "never", incremental: bool = False) -> Dict[str, List]:
     """``bo_loop.run_mobo`` with the discrete-KG strategy for ``n_iter`` BO steps; returns the
     query history (x, objective index or None for full evaluation, observed values, acquisition).
     With ``catalog`` it also writes the reference's checkpoints and query-history table under
     ``run_key`` (default ``eval_separate`` / ``eval_full``).  ``fit_hyperparams`` (``bo_loop.py:574-619``):
     ``never`` and ``once`` use ``hyper`` as given (``once``: the fitted values with their ``noises``);
     ``always`` refits on the observations before every model use, the constant means fixed at the first
-    fit's (``:600-614``)."""
+    fit's (``:600-614``).  ``incremental`` (``never`` / ``once`` only: with ``always`` the hyperparameters change
+    at every step and it is ignored) turns ``set_incremental_state`` on for the run, so each step's device
+    state comes from the previous one by appending the new observations instead of a full rebuild; the
+    switch is restored afterwards."""
     if fit_hyperparams not in ("never", "once", "always"):
         raise ValueError(f"Unexpected value for fit_hyperparams. Got {fit_hyperparams!r}")
+    on = incremental and fit_hyperparams != "always"
+    prev = set_incremental_state(True) if on else None
+    try:
+        return _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations, spec, seed, catalog,
+                         run_key, fit_hyperparams)
+    finally:
+        if on:
+            set_incremental_state(prev)
+
+
+def _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations, spec, seed, catalog, run_key,
+              fit_hyperparams) -> Dict[str, List]:
     m, d = problem.num_objectives, problem.gp.input_dim
     # the pipeline's --seed (main.py:235, utils.set_random_seed): every later draw comes from the global RNG, as
     # in the reference -- the initial Sobol points (generate_initial_data, bo_loop.py:48-49: no seed), each
@@ -221,12 +236,13 @@ def run_mobo(problem: GPProblem, hyper: Dict[str, Sequence[float]], separate: bo
 
 
 def run_smoke(problem: GPProblem, hyper: Dict[str, Sequence[float]], seed: int = 0,
-              catalog: Optional[DataCatalog] = None, fit_hyperparams: str = "never") -> Dict[str, Dict]:
+              catalog: Optional[DataCatalog] = None, fit_hyperparams: str = "never",
+              incremental: bool = False) -> Dict[str, Dict]:
     """``run_pipeline`` under ``SMOKE_TEST`` (``main.py:171-216``): the separate-evaluation run and
     the full-evaluation run, two BO steps each; with ``catalog`` both write the reference's files.
     ``fit_hyperparams = "once"`` fits the hyperparameters first (``main.py:181-182``, saved to the catalog's
     ``hyperparameters.pt`` as the fitted surrogate's state dict) and both runs use them; ``"always"`` refits
-    inside the runs."""
+    inside the runs.  ``incremental``: as ``run_mobo``'s."""
     if fit_hyperparams == "once":
         torch.manual_seed(seed)
         cfg = reference_model_config(problem.num_objectives, problem.bounds, "once")
@@ -237,6 +253,6 @@ def run_smoke(problem: GPProblem, hyper: Dict[str, Sequence[float]], seed: int =
             catalog.save_model_hyperparameters(
                 to_state_dict(surrogate([x] * problem.num_objectives, [y] * problem.num_objectives, hyper), cfg))
     return {"separate": run_mobo(problem, hyper, separate=True, seed=seed, catalog=catalog,
-                                 fit_hyperparams=fit_hyperparams),
+                                 fit_hyperparams=fit_hyperparams, incremental=incremental),
             "full": run_mobo(problem, hyper, separate=False, seed=seed, catalog=catalog,
-                             fit_hyperparams=fit_hyperparams)}
+                             fit_hyperparams=fit_hyperparams, incremental=incremental)}

@@ -28,8 +28,8 @@ from typing import Optional
 import torch
 from torch import Tensor
 
-from . import _lib
-from .errors import BotorchTensorDimensionError, UnsupportedError
+from . import _lib, gp_state
+from .errors import BotorchTensorDimensionError, NotPSDError, UnsupportedError
 from .gp_state import DeviceGPState, current_stream_ptr
 from .model import ModelListGPState, SingleTaskGPState, from_botorch
 
@@ -155,6 +155,35 @@ def clear_state_cache() -> None:
     _STATE_CACHE.clear()
 
 
+def _extended_state(state: ModelListGPState, D: Tensor, dev) -> Optional[DeviceGPState]:
+    """The incremental path (``set_incremental_state``): a cached state on ``dev`` over an equal
+    discretisation whose model ``state`` extends (``gp_state.match_extension``), grown by appending the added
+    rows one at a time (``DeviceGPState.with_observation``, the bordered Cholesky update).  ``None`` when no
+    entry matches, or when an append is not positive definite under the old jitter: the caller then builds
+    the state in full, which applies the jitter policy."""
+    for efp, eD, edev, est, _ in _STATE_CACHE:
+        if edev != dev or eD.shape != D.shape or eD.dtype != D.dtype or not torch.equal(eD, D.to(eD.device)):
+            continue
+        added = gp_state.match_extension(est.model, state)
+        if added is None or not any(added):
+            continue
+        st, done = est, 0
+        try:
+            for i, k in enumerate(added):
+                new = state.models[i]
+                n0 = new.num_train - k
+                for r in range(k):
+                    st = st.with_observation(i, new.train_x[n0 + r], train_y=new.train_y[:n0 + r + 1])
+                    done += 1
+        except NotPSDError:
+            gp_state._STATS["append_fallbacks"] += 1
+            return None
+        gp_state._STATS["appends"] += done
+        st.model = state
+        return st
+    return None
+
+
 def shared_state(state: ModelListGPState, fp, x_discretisation: Tensor, device, owner=None) -> DeviceGPState:
     """The cached DeviceGPState of (model fingerprint ``fp``, discretisation values, device), or a new one.
     ``owner`` (the caller's model object) is kept alive with the entry, with its fingerprinted tensors."""
@@ -164,7 +193,10 @@ def shared_state(state: ModelListGPState, fp, x_discretisation: Tensor, device, 
         if efp == fp and edev == dev and eD.shape == D.shape and eD.dtype == D.dtype and torch.equal(eD, D.to(eD.device)):
             _STATE_CACHE.insert(0, _STATE_CACHE.pop(i))
             return est
-    st = DeviceGPState(state, x_discretisation, dev)
+    st = _extended_state(state, D, dev) if gp_state.incremental_state() else None
+    if st is None:
+        st = DeviceGPState(state, x_discretisation, dev)
+        gp_state._STATS["full_builds"] += 1
     _STATE_CACHE.insert(0, (fp, D.clone(), dev, st, owner))
     del _STATE_CACHE[_STATE_CACHE_SIZE:]
     return st

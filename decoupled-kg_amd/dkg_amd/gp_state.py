@@ -58,6 +58,7 @@ class OutputCache:
     L: torch.Tensor
     jitter: float = 0.0  # absolute jitter psd_safe_cholesky needed (0: none)
     struct: _lib.DkgOutput = field(repr=False, default=None)
+    Linv: torch.Tensor = field(repr=False, default=None)  # L^{-1}, row-major n x n (append_observation reads it)
 
 
 def _base_struct(st: SingleTaskGPState, inv_ls, train_x) -> _lib.DkgOutput:
@@ -127,8 +128,114 @@ def prepare_outputs(models, D: torch.Tensor) -> List[OutputCache]:
                        "dkg_cross_root")
         o.disc_frag = _lib.ptr(disc_frag)
         o.disc_mean = _lib.ptr(disc_mean)
-        caches.append(OutputCache(st, inv_ls, X, alpha, root_frag, disc_frag, disc_mean, L, jit[i], o))
+        n = o.n
+        linv = work[: n * n * 8].view(torch.double).view(n, n)  # the head of the preparation's scratch
+        caches.append(OutputCache(st, inv_ls, X, alpha, root_frag, disc_frag, disc_mean, L, jit[i], o, linv))
     return caches
+
+
+def append_observation(cache: OutputCache, D: torch.Tensor, x, train_y) -> OutputCache:
+    """The caches of ``([X; x], train_y)`` from those of ``(X, y)`` by the bordered Cholesky update
+    (``dkg_append_observation``): no refactorisation, one pass over ``L^{-1}`` and one over ``disc_frag``.
+    ``D`` is the device discretisation the cache was built over, ``x`` the new point (d values),
+    ``train_y`` the n + 1 targets of the grown output (model space).  Out of place: ``cache`` and its
+    tensors are left as they are.  Raises ``NotPSDError`` when the grown covariance is not positive
+    definite under the old jitter (rebuild instead: the full preparation applies the jitter policy) and
+    ``UnsupportedError`` beyond 1024 training points."""
+    lib = _lib.load()
+    st = cache.state
+    dev = D.device
+    n, d = cache.train_x.shape
+    N = D.shape[0]
+    if _pad16(n + 1) > 1024:
+        raise UnsupportedError(f"n={n + 1} training points > 1024 per output is not supported")
+    xh = torch.as_tensor(x, dtype=torch.double).detach().cpu().reshape(1, d)
+    yh = torch.as_tensor(train_y, dtype=torch.double).detach().cpu().reshape(-1)
+    if yh.numel() != n + 1:
+        raise ValueError(f"train_y has {yh.numel()} entries for {n + 1} training points")
+    new_st = SingleTaskGPState(torch.cat([st.train_x, xh]), yh.clone(), st.lengthscale, st.outputscale, st.noise,
+                               st.mean_constant, st.kernel, st.nu, st.y_mean, st.y_std)
+    flat = torch.cat([xh.reshape(-1), yh]).to(dev)  # the new point and the targets in one host-to-device copy
+    X = torch.cat([cache.train_x, flat[:d].view(1, d)])
+    y = flat[d:]
+    n1 = n + 1
+    L = torch.empty(n1, n1, dtype=torch.double, device=dev)
+    linv = torch.empty(n1, n1, dtype=torch.double, device=dev)
+    alpha = torch.empty(_pad16(n1), dtype=torch.double, device=dev)
+    root_frag = torch.empty(lib.dkg_frag_elems(n1, n1), dtype=torch.double, device=dev)
+    disc_frag = torch.empty(max(1, lib.dkg_frag_elems(N, n1)), dtype=torch.double, device=dev)
+    disc_mean = torch.empty(max(16, _pad16(N)), dtype=torch.double, device=dev)
+    work = torch.empty(lib.dkg_append_workspace(n, N), dtype=torch.uint8, device=dev)
+    _lib.check(lib.dkg_append_observation(cache.struct, d, _lib.ptr(cache.L), _lib.ptr(cache.Linv), _lib.ptr(D), N,
+                                          _lib.ptr(X), _lib.ptr(y), float(cache.jitter), _lib.ptr(L), _lib.ptr(linv),
+                                          _lib.ptr(alpha), _lib.ptr(root_frag), _lib.ptr(disc_frag),
+                                          _lib.ptr(disc_mean), _lib.ptr(work), work.numel(),
+                                          current_stream_ptr(dev)), "dkg_append_observation")
+    o = _base_struct(new_st, cache.inv_ls, X)
+    o.alpha = _lib.ptr(alpha)
+    o.root_frag = _lib.ptr(root_frag)
+    o.disc_frag = _lib.ptr(disc_frag)
+    o.disc_mean = _lib.ptr(disc_mean)
+    return OutputCache(new_st, cache.inv_ls, X, alpha, root_frag, disc_frag, disc_mean, L, cache.jitter, o, linv)
+
+
+# The opt-in incremental path of discretekg.shared_state (off by default: nothing that exists changes bits)
+# and the counters of how the shared device states were made.
+_INCREMENTAL = False
+_STATS = {"full_builds": 0, "appends": 0, "append_fallbacks": 0}
+
+
+def set_incremental_state(on: bool) -> bool:
+    """With the switch on, a model that extends a cached one (same discretisation and hyperparameters, rows
+    added to some outputs) gets its device state by appending the added rows to the cached state
+    (``DeviceGPState.with_observation``) instead of a full rebuild.  Returns the previous setting."""
+    global _INCREMENTAL
+    prev = _INCREMENTAL
+    _INCREMENTAL = bool(on)
+    return prev
+
+
+def incremental_state() -> bool:
+    return _INCREMENTAL
+
+
+def state_stats() -> dict:
+    """How the shared device states were made since the last reset: ``full_builds`` (a whole
+    ``DeviceGPState``), ``appends`` (rows appended) and ``append_fallbacks`` (an append that was not positive
+    definite, answered by a full build)."""
+    return dict(_STATS)
+
+
+def reset_state_stats() -> None:
+    for k in _STATS:
+        _STATS[k] = 0
+
+
+def _same_hyperparameters(a: SingleTaskGPState, b: SingleTaskGPState) -> bool:
+    return (a.kernel == b.kernel and (a.kernel == "rbf" or float(a.nu) == float(b.nu))
+            and float(a.outputscale) == float(b.outputscale) and float(a.noise) == float(b.noise)
+            and float(a.mean_constant) == float(b.mean_constant) and float(a.y_mean) == float(b.y_mean)
+            and float(a.y_std) == float(b.y_std) and a.lengthscale.shape == b.lengthscale.shape
+            and torch.equal(a.lengthscale, b.lengthscale))
+
+
+def match_extension(old: ModelListGPState, new: ModelListGPState):
+    """Whether ``new`` extends ``old``: per output the number of rows added (0: equal data), or ``None`` when
+    it does not.  An output extends its old self when it has equal data, or the same hyperparameters, kernel,
+    nu, ``y_mean`` and ``y_std``, the old rows of ``train_x`` equal by value, and k >= 1 rows added (its
+    targets may all be new).  Pure host code."""
+    if old.num_outputs != new.num_outputs or old.input_dim != new.input_dim:
+        return None
+    added = []
+    for a, b in zip(old.models, new.models):
+        n = a.num_train
+        k = b.num_train - n
+        if k < 0 or not _same_hyperparameters(a, b) or not torch.equal(a.train_x, b.train_x[:n]):
+            return None
+        if k == 0 and not torch.equal(a.train_y, b.train_y):
+            return None
+        added.append(k)
+    return added
 
 
 def prepare_output(st: SingleTaskGPState, D: torch.Tensor) -> OutputCache:
@@ -157,6 +264,33 @@ class DeviceGPState:
         self.structs = (_lib.DkgOutput * self.m)(*[c.struct for c in self.outputs])
         self._ws = None
         self._ws_key = None
+
+    def with_observation(self, output_ix: int, x, y=None, train_y=None) -> "DeviceGPState":
+        """A new state with ``x`` appended to output ``output_ix``: that output's caches by the bordered
+        update (``append_observation``), the other outputs' ``OutputCache`` objects shared, not copied.
+        Give the new target ``y`` (appended to the output's targets) or the n + 1 targets ``train_y``.  This
+        state, and every plan or captured graph on it, stays valid.  Raises ``NotPSDError`` /
+        ``UnsupportedError`` as ``append_observation``."""
+        if not 0 <= int(output_ix) < self.m:
+            raise IndexError(f"output index {output_ix} out of range for {self.m} outputs")
+        if (y is None) == (train_y is None):
+            raise ValueError("give exactly one of y (the new target) and train_y (all n + 1 targets)")
+        i = int(output_ix)
+        old = self.outputs[i]
+        if train_y is None:
+            train_y = torch.cat([old.state.train_y, torch.as_tensor(y, dtype=torch.double).detach().cpu().reshape(1)])
+        with torch.cuda.device(self.device):
+            new = append_observation(old, self.D, x, train_y)
+        st = object.__new__(DeviceGPState)
+        st.device = self.device
+        st.D, st.N, st.d, st.m = self.D, self.N, self.d, self.m
+        st.outputs = list(self.outputs)
+        st.outputs[i] = new
+        st.model = ModelListGPState(*[c.state for c in st.outputs])
+        st.structs = (_lib.DkgOutput * st.m)(*[c.struct for c in st.outputs])
+        st._ws = None
+        st._ws_key = None
+        return st
 
     def plan(self, W: torch.Tensor, target, max_B: int, grad: bool = False, force_walk: bool = False,
              f32: bool = False, fused: bool = False, no_chain: bool = False) -> "ForwardPlan":

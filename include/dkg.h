@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define DKG_ABI_VERSION 8  /* 8: dkg_plan_forward_batches, dkg_plan_time_stage_batches; 7: DKG_PLAN_NO_CHAIN */
+#define DKG_ABI_VERSION 9  /* 9: dkg_append_observation; 8: dkg_plan_forward_batches, dkg_plan_time_stage_batches */
 #define DKG_MAX_OUTPUTS 8   /* outputs (objectives) per model list */
 #define DKG_MAX_DIM 16      /* input dimension d */
 
@@ -129,6 +129,39 @@ int dkg_pack_root(const double* r, int n, double* root_frag, void* stream);
  * discretisation D it builds disc_frag / disc_mean. */
 int dkg_cross_root(const dkg_output* o, int d, const double* x, int rows, double* q_frag,
                    double* mean, void* stream);
+
+/* Bytes of device scratch dkg_append_observation needs (n training points before the append, N
+ * discretisation points); 0 for n < 1 or N < 0. */
+size_t dkg_append_workspace(int n, int N);
+
+/* One observation appended to an output's fitted state without refactorising: from the caches of
+ * (X, y) those of ([X; x_new], y'), by the bordered Cholesky in fp64.  The reference rebuilds its model,
+ * and every cache behind model.posterior (discretekg.py:182-185), at each BO iteration
+ * (bo_loop.py:457-465); a decoupled step adds one row to one output and leaves the others alone.
+ * With M = L^{-1}, k = s kappa(X, x_new), r' = y' - c:
+ *   l = M k, lambda^2 = s kappa(x, x) + noise + jitter - l.l
+ *   L' = [[L, 0], [l^T, lambda]],  M' = [[M, 0], [-(l^T M) / lambda, 1 / lambda]]
+ *   alpha' = M'^T M' r',  Q_D' = [Q_D, (s kappa(D, x_new) - Q_D l) / lambda],  mu_D' = c + Q_D' M' r'
+ *   o       : the old state: n, kernel, hyperparameters, inv_lengthscale, disc_frag (N_pad x n_pad(n);
+ *             train_x, alpha, root_frag and disc_mean are not read)
+ *   L, Linv : device [n x n] row-major, the old L and L^{-1} (dkg_prepare_output's L and the head of its work)
+ *   disc    : device [N x d], the discretisation the old disc_frag was built over (nullable when N = 0,
+ *             as are o->disc_frag, disc_frag_new and disc_mean_new)
+ *   train_x : device [(n + 1) x d], its last row x_new;  train_y: device [n + 1], the new targets y'
+ *             (the old ones with y_new appended, or wholly new values)
+ *   jitter  : the absolute jitter the old factorisation used (dkg_prepare_output's jitter_used)
+ *   L_new, Linv_new [(n + 1)^2], alpha_new [n_pad(n + 1)], root_frag_new [n_pad(n + 1)^2],
+ *   disc_frag_new [N_pad x n_pad(n + 1)], disc_mean_new [N_pad]: device, written; padding exactly zero.
+ *   work    : device scratch of dkg_append_workspace(n, N) bytes.
+ * Out of place: nothing of the old state is written, so plans and captured graphs on it stay valid.
+ * Stream ordered; synchronises `stream` once to read the status.  DKG_ERR_NOT_PD when lambda^2 <= 0 or is
+ * not finite (the outputs are then not to be used: rebuild with dkg_prepare_output, which applies the
+ * jitter policy), DKG_ERR_UNSUPPORTED when n_pad(n + 1) > 1024, DKG_ERR_ARG for NULL pointers or bad
+ * sizes; the arguments are checked before any HIP call.  Deterministic: every sum runs in a fixed order. */
+int dkg_append_observation(const dkg_output* o, int d, const double* L, const double* Linv, const double* disc, int N,
+                           const double* train_x, const double* train_y, double jitter, double* L_new,
+                           double* Linv_new, double* alpha_new, double* root_frag_new, double* disc_frag_new,
+                           double* disc_mean_new, void* work, size_t work_bytes, void* stream);
 
 /* Bytes of scratch dkg_forward needs for (m outputs, N points, B candidates, S weights). */
 size_t dkg_forward_workspace(const dkg_output* outs, int m, int N, int B, int S);
