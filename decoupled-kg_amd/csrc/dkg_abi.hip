@@ -810,6 +810,24 @@ int dkg_debug_cov_kernels(int mask) {
   return set_cov_enabled(mask);
 }
 
+int dkg_debug_cross_tall(int mode) {
+  if (mode < -1 || mode > 1) {
+    fail(DKG_ERR_ARG, "dkg_debug_cross_tall: mode=%d (-1 default, 0 never, 1 every eligible shape)", mode);
+    return -2;
+  }
+  return set_cross_tall_mode(mode);
+}
+
+long long dkg_debug_cross_tall_launches(void) { return cross_tall_launches(); }
+
+int dkg_debug_cross_tall_eligible(int max_n_pad, int d, int B, int f32) {
+  if (max_n_pad < 16 || max_n_pad % 16 != 0 || d < 1 || d > DKG_MAX_DIM || B < 1) {
+    fail(DKG_ERR_ARG, "dkg_debug_cross_tall_eligible: max_n_pad=%d d=%d B=%d", max_n_pad, d, B);
+    return -2;
+  }
+  return cross_tall_eligible(max_n_pad, d, B, f32 != 0) ? 1 : 0;
+}
+
 int dkg_debug_wave_ops(const double* in, double* out, void* stream) {
   if (!in || !out) return fail(DKG_ERR_ARG, "NULL pointer");
   return hip_check(launch_debug_wave(in, out, (hipStream_t)stream), "debug_wave_kernel");

@@ -41,6 +41,8 @@ __host__ __device__ inline bool cross_kfill(int np) { return DKG_CROSS_KFILL && 
 // Launches over many candidates (a launch of several forward batches, dkg_plan_forward_batches) fill K(x, X)
 // once with the separate kernel at any n: the fill replicated over the column-pair groups of a row tile (~4.5x
 // at n = 256) is then work the whole device waits on, not latency one forward hides.  Same bits either way.
+// fp64 plans at n_pad <= 256 take cross_tall_kernel there instead (dkg_stages.h: K(x, X) once per row tile, in LDS);
+// the fill by candidate count remains for fp32 plans (Plan::kx32).
 #ifndef DKG_KFILL_MIN_B
 #define DKG_KFILL_MIN_B 512
 #endif
@@ -208,6 +210,12 @@ constexpr int KST_WG = 1024;
 hipError_t launch_debug_wave(const double* in, double* out, hipStream_t s);
 // The opt-in fp64 covariance block kernels (dkg_debug_cov_kernels): sets the mask, returns the previous one.
 int set_cov_enabled(int mask);
+// cross_tall_kernel's dispatch (dkg_debug_cross_tall): sets the mode (-1 default rule, 0 never, 1 every eligible
+// shape), returns the previous one; the launches that took the kernel so far; and whether a stage-0 launch of B
+// candidates of a plan (widest n_pad, d, fp32 or not) takes it under the current mode.
+int set_cross_tall_mode(int mode);
+long long cross_tall_launches();
+bool cross_tall_eligible(int max_np, int d, int B, bool f32);
 hipError_t launch_debug_mfma(const double* a, const double* b, double* c, hipStream_t s);
 
 // Launch geometry of the envelope stage for (B, S): waves per workgroup and

@@ -6,6 +6,7 @@
 //   envelope_kernel     lines a_k + b_k z per (candidate, scalarisation), upper
 //                       envelope, closed-form Gaussian expectation, mean over S
 #include "dkg_fused.h"
+#include <atomic>
 #include <cstdlib>
 
 namespace dkg {
@@ -243,6 +244,24 @@ __global__ __launch_bounds__(XB_WAVES * WAVE) __attribute__((amdgpu_waves_per_eu
   }
   if (DKG_ABLATIONS && (P->debug_cov & 32)) return;  // probe: the Q_X blocks alone
   cross_means_body(P, B, kg, blockIdx.x - nbig);
+}
+
+// The cross stage of a many-candidate fp64 launch at n_pad <= 256 in one launch with K(x, X) kept in LDS
+// (cross_tall_body): grid (row blocks of RT candidate tiles, outputs); the workgroups of output 0 clear their
+// tiles' accumulators as cross_big_kernel's means workgroups do.
+template <int DM, int RT>
+__global__ __launch_bounds__(XT_WAVES * WAVE) void cross_tall_kernel(const Plan* __restrict__ P,
+                                                                    const double* __restrict__ xnew, int B,
+                                                                    double* __restrict__ kg, int dst) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  unsigned long long* st = kst_slot(dst, P, 0);
+  KST_BEGIN(st);
+  const int oi = blockIdx.y;
+  if (oi == 0)
+    for (int h = 0; h < RT; ++h)
+      if (((int)blockIdx.x * RT + h) * 16 < B) clear_tile_accumulators(P, kg, B, blockIdx.x * RT + h);
+  if (DKG_ABLATIONS && (__builtin_amdgcn_readfirstlane(P->debug_cov) & 2)) return;  // ablation: empty cross stage
+  cross_tall_body<DM, RT>(P, xnew, B, blockIdx.x, oi, smem, st);
 }
 
 // The fp32 plan's cross stage with the K(x, X) fill (DKG_PLAN_F32, e.g. BASELINE configs[4]): the 64 x 32 blocks
@@ -633,6 +652,36 @@ static bool cross_big() {
   return !env || std::atoi(env) != 0;
 }
 
+// cross_tall_kernel's dispatch (dkg_debug_cross_tall): -1 the default rule, 0 never, 1 every eligible shape
+// whatever the candidate count.  Atomics: the launcher threads read the mode while a test may set it.
+// DKG_CROSS_TALL=0 / 1 (A/B measurements) sets the initial mode.
+static std::atomic<int> g_cross_tall_mode{-2};  // -2: from the environment at first use
+static std::atomic<long long> g_cross_tall_launches{0};
+static int cross_tall_mode() {
+  int mode = g_cross_tall_mode.load(std::memory_order_relaxed);
+  if (mode == -2) {
+    const char* env = std::getenv("DKG_CROSS_TALL");
+    const int from_env = !env ? -1 : (std::atoi(env) != 0 ? 1 : 0);
+    // (a concurrent set_cross_tall_mode wins)
+    g_cross_tall_mode.compare_exchange_strong(mode, from_env, std::memory_order_relaxed);
+    mode = g_cross_tall_mode.load(std::memory_order_relaxed);
+  }
+  return mode;
+}
+int set_cross_tall_mode(int mode) {
+  const int prev = cross_tall_mode();
+  g_cross_tall_mode.store(mode < 0 ? -1 : (mode > 0 ? 1 : 0), std::memory_order_relaxed);
+  return prev;
+}
+long long cross_tall_launches() { return g_cross_tall_launches.load(std::memory_order_relaxed); }
+// fp64 plans whose widest output fits one column-tile pair per wave (n_pad <= 256) and whose slab fits the CU's
+// LDS; by default the launches that would otherwise fill K(x, X) with the separate kernel by candidate count.
+bool cross_tall_eligible(int max_np, int d, int B, bool f32) {
+  const int mode = cross_tall_mode();
+  if (mode == 0 || f32 || B < 1 || d < 1 || !cross_tall_fits(max_np, d, XT_RT)) return false;
+  return mode == 1 || B >= KFILL_MIN_B;
+}
+
 // The big blocks' order (block_order).  Measured per launch (L2 fetch x2 / write MB, stage us; DESIGN.md 4.7,
 // profiles/r05/cov_order): stress (nbx 64, nby 4, m 3): order 0 363 / 37, 1 263 / 36, 2 145 / 101, 3 152 / 101,
 // all 143 us; headline x 10 (nbx 16, nby 20, m 2): 0 49 / 21, 1 72 / 21, 2 44 / 42, all 47 us.  Orders 2 / 3
@@ -650,6 +699,18 @@ template <int DM, class T>
 static hipError_t launch_cross_cov_tt(const Plan& h, const Plan* dev, const double* xnew, int B, double* kg,
                                       hipStream_t s, int stage, int geom_B) {
   if (stage == 0) {
+    if constexpr (sizeof(T) == 8) {
+      // one launch, K(x, X) evaluated once per row block and kept in LDS (no cross_kfill_kernel, no Plan::kx)
+      if (cross_tall_eligible(h.max_np, h.d, B, false)) {
+        const dim3 grid((pad16(B) / 16 + XT_RT - 1) / XT_RT, h.m);
+        const size_t lds = cross_tall_lds_bytes(h.max_np, h.d, XT_RT);
+        g_cross_tall_launches.fetch_add(1, std::memory_order_relaxed);
+        raise_lds_limit((const void*)cross_tall_kernel<DM, XT_RT>, lds);
+        hipLaunchKernelGGL((cross_tall_kernel<DM, XT_RT>), grid, dim3(XT_WAVES * WAVE), lds, s, dev, xnew, B, kg,
+                           h.debug_stamp);
+        return hipGetLastError();
+      }
+    }
     const int use_kx = (h.kx[0] != nullptr && cross_kfill_launch(h.max_np, B)) ? 1 : 0;
     if (use_kx) {
       dim3 kgrid(pad16(B) / 16, (h.max_np / 4 + KF_KB - 1) / KF_KB, h.m);

@@ -2032,6 +2032,210 @@ __device__ __forceinline__ void cross_big_body(const Plan* __restrict__ P, int B
 }
 
 // ---------------------------------------------------------------------------
+// cross_tall_kernel (fp64 forward, n_pad <= 256, launches of many candidates): the whole cross stage of RT
+// candidate tiles and one output in one workgroup, K(x, X) never leaving the CU.  The workgroup stages the
+// pre-scaled training inputs and alpha, evaluates its 16 RT x n slab of s k(x, X) once into LDS in B-operand
+// order (pair-packed as frag_index, so a lane reads the k-blocks 2 j, 2 j + 1 of a candidate tile with one
+// ds_read_b128), and wave p then owns the column-tile pair (p, T - 1 - p) of Q_X -- 4 (T + 1) k-blocks per
+// candidate tile whatever p, the balance cross_root_impl's pairs have -- streaming the pair's R^T fragments
+// from root_frag (L2) into registers once for all RT candidate tiles.
+// Same bits as cross_root_impl, element for element:
+//   fill   cross_kernel_term on the LDS copy of the inputs; thread (wave w, lane l) evaluates the k-blocks
+//          w, w + 8, ... of lane l, which is cross_root_impl's e = tid + 512 it, so its mean partial runs the
+//          same fma chain; partner sums, then the 8 waves in order.
+//   Q_X    column tile tj over the words j < 2 (tj + 1), in chunks of CW = ceil(2 (max(tj, T - 1 - tj) + 1) / 8)
+//          words; k-blocks 2 j / 2 j + 1 on chains 0 / 1, the chains added and joined to the running sum at
+//          every chunk end and at the tile's extent (cross_big_body's replay of the split-K reduction; chunks
+//          past the extent add + 0.0 there and are skipped here).
+// The wave's two tiles are one stream of words (tile p's, then tile T - 1 - p's), so the R^T loads of the
+// second tile are in flight under the first's MFMAs; a tile's sums are stored at its last word.
+#ifndef DKG_XT_RT
+#define DKG_XT_RT 1
+#endif
+// Candidate tiles per workgroup.  1: a 5-batch headline launch is 80 workgroups of a 32 KiB slab, 14.0 us alone;
+// 2 (64 KiB slabs, R^T streamed half as often, 40 workgroups) 20.4 us, and the same rate with four streams in
+// flight (profiles/cross_tall): the workgroup's lifetime is its fill plus its MFMAs, both proportional to RT.
+constexpr int XT_RT = DKG_XT_RT;
+constexpr int XT_WAVES = CR_WAVES;  // the fill's thread map is cross_root_impl's
+constexpr int XT_U = 8;             // R^T words per load batch (two batches in registers)
+constexpr int XT_MAX_NP = 16 * 2 * XT_WAVES;  // one column-tile pair per wave
+
+// LDS doubles: the slab [rt][np / 8][64] words, the mean partials [rt][8][16], the inputs [np][d], alpha [np].
+__host__ __device__ inline size_t cross_tall_lds_bytes(int np, int d, int rt) {
+  return ((size_t)rt * 16 * np + (size_t)rt * XT_WAVES * 16 + (size_t)np * d + np) * sizeof(double);
+}
+// The shapes the kernel takes: every output's n_pad within one pair per wave, the slab within a CU's LDS.
+__host__ __device__ inline bool cross_tall_fits(int max_np, int d, int rt) {
+  return CR_WAVES == 8 && max_np >= 16 && max_np <= XT_MAX_NP && cross_tall_lds_bytes(max_np, d, rt) <= 160 * 1024;
+}
+
+template <int DM, int RT>
+__device__ __forceinline__ void cross_tall_body(const Plan* __restrict__ P, const double* __restrict__ x, int B,
+                                                int rb, int oi, double* smem, unsigned long long* st) {
+  const dkg_output& o = P->o[oi];
+  const int d = P->d;
+  const int n = o.n, np = pad16(n), T = np / 16, KB = np / 4, KP = KB / 2;
+  const int RTall = pad16(B) / 16, ti0 = rb * RT;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  double* slabd = smem;                                          // [RT][KP][64] words of two k-blocks
+  const double2* slab = reinterpret_cast<const double2*>(smem);
+  double* mred = smem + (size_t)RT * 16 * np;                    // [RT][XT_WAVES][16]
+  double* xs = mred + RT * XT_WAVES * 16;                        // [n][d] staged training inputs
+  double* als = xs + (size_t)np * d;                             // [n] alpha
+  const double* __restrict__ root = o.root_frag;
+
+  // the wave's stream of R^T words: tile tA's EA words, then tile tB's EB (the middle tile of an odd T: tB alone)
+  const int tA = wave, tB = T - 1 - wave;
+  const bool active = tA <= tB;
+  const int EA = (active && tA != tB) ? 2 * (tA + 1) : 0, EB = active ? 2 * (tB + 1) : 0, ES = EA + EB;
+  const int CW = (2 * (tB + 1) + CR_WAVES - 1) / CR_WAVES;
+  auto load_batch = [&](double2 (&r)[XT_U], int s0) {
+#pragma unroll
+    for (int u = 0; u < XT_U; ++u) {
+      const int s = min(s0 + u, ES - 1);
+      r[u] = frag_pair(root, s < EA ? tA : tB, s < EA ? s : s - EA, lane, KB);
+    }
+  };
+  double2 r0[XT_U], r1[XT_U];
+  if (active) load_batch(r0, 0);  // in flight during the staging and the fill
+
+  KST(st, 2);
+  for (int e = tid; e < n * d; e += XT_WAVES * WAVE) xs[e] = o.train_x[e] * o.inv_lengthscale[e % d];
+  for (int e = tid; e < n; e += XT_WAVES * WAVE) als[e] = o.alpha[e];
+  bool rv[RT];
+  double xr[RT][DM];  // the candidate rows, pre-scaled (clamped loads, no branches)
+#pragma unroll
+  for (int h = 0; h < RT; ++h) {
+    const int row = (ti0 + h) * 16 + (lane & 15);
+    rv[h] = row < B;
+    const int rowc = min(row, B - 1);
+#pragma unroll
+    for (int k = 0; k < DM; ++k) {
+      const int kk = min(k, d - 1);
+      xr[h][k] = x[(size_t)rowc * d + kk] * o.inv_lengthscale[kk];
+    }
+  }
+  __syncthreads();
+
+  KST(st, 3);
+  // ---- the slab K(x_row, X_col) in B-operand order (zero outside B x n) and the mean partials
+  double mpart[RT];
+#pragma unroll
+  for (int h = 0; h < RT; ++h) mpart[h] = 0.0;
+  const double os = o.outputscale;
+  const int iters = (KB + XT_WAVES - 1) / XT_WAVES;  // cross_root_impl's trip count for the widest pair
+  auto fill_loop = [&](auto kind_c) {
+    constexpr int KIND = decltype(kind_c)::value;
+    const const_dptr tab = psi_tab();
+#pragma unroll 2
+    for (int it = 0; it < iters; ++it) {
+      const int kb = wave + it * XT_WAVES;
+      const int col = 4 * kb + (lane >> 4);
+      const int cc = min(col, n - 1);
+      const double al = als[cc];
+#pragma unroll
+      for (int h = 0; h < RT; ++h) {
+        const double kv = cross_kernel_term<DM, KIND>(xr[h], xs + (size_t)cc * d, d, os, tab);
+        const double v = (rv[h] && col < n) ? kv : 0.0;
+        mpart[h] = fma(v, al, mpart[h]);
+        if (kb < KB) slabd[(((size_t)h * KP + (kb >> 1)) * 64 + lane) * 2 + (kb & 1)] = v;
+      }
+    }
+  };
+  switch (o.kernel) {
+    case DKG_MATERN12: fill_loop(std::integral_constant<int, DKG_MATERN12>{}); break;
+    case DKG_MATERN32: fill_loop(std::integral_constant<int, DKG_MATERN32>{}); break;
+    case DKG_RBF: fill_loop(std::integral_constant<int, DKG_RBF>{}); break;
+    default: fill_loop(std::integral_constant<int, DKG_MATERN52>{}); break;
+  }
+  // mean partials: lanes l, l^16, l^32, l^48 share a row.
+#pragma unroll
+  for (int h = 0; h < RT; ++h) {
+    double v = mpart[h];
+    v += partner_f64<4>(v);
+    v += partner_f64<5>(v);
+    if (lane < 16) mred[(h * XT_WAVES + wave) * 16 + lane] = v;
+  }
+  __syncthreads();
+
+  KST(st, 4);
+  if (tid < 16 * RT) {
+    const int h = tid >> 4, r = tid & 15;
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < XT_WAVES; ++w) s += mred[(h * XT_WAVES + w) * 16 + r];
+    const int rr = (ti0 + h) * 16 + r;
+    if (ti0 + h < RTall) P->mux[oi][rr] = (rr < B) ? o.mean_constant + s : 0.0;
+  }
+  if (active) {
+    double* __restrict__ qout = P->q[oi];
+    d4 ch[RT][2], sum[RT];
+#pragma unroll
+    for (int h = 0; h < RT; ++h) sum[h] = ch[h][0] = ch[h][1] = d4{0.0, 0.0, 0.0, 0.0};
+    int seg_left = CW;  // words left in the current chunk of cross_root_impl's split
+    auto run_batch = [&](const double2 (&r)[XT_U], int s0) __attribute__((always_inline)) {
+      // the batch's slab words first, all in flight at once: read under the flush branches below, every word's
+      // read waited for by the MFMAs right behind it (116 cycles per MFMA against the pipe's 64)
+      double2 bw[XT_U][RT];
+#pragma unroll
+      for (int u = 0; u < XT_U; ++u) {
+        const int s = min(s0 + u, ES - 1);
+        const int j = s < EA ? s : s - EA;
+#pragma unroll
+        for (int h = 0; h < RT; ++h) bw[u][h] = slab[((size_t)h * KP + j) * 64 + lane];
+      }
+#pragma unroll
+      for (int u = 0; u < XT_U; ++u) {
+        const int s = s0 + u;
+        if (s >= ES) break;  // wave-uniform
+        const bool inA = s < EA;
+        const int j = inA ? s : s - EA;
+#pragma unroll
+        for (int h = 0; h < RT; ++h) {
+          ch[h][0] = mfma_f64(r[u].x, bw[u][h].x, ch[h][0]);
+          ch[h][1] = mfma_f64(r[u].y, bw[u][h].y, ch[h][1]);
+        }
+        const bool last = j + 1 == (inA ? EA : EB);
+        if (--seg_left == 0 || last) {  // wave-uniform
+          seg_left = CW;
+#pragma unroll
+          for (int h = 0; h < RT; ++h) {
+            sum[h] += ch[h][0] + ch[h][1];
+            ch[h][0] = ch[h][1] = d4{0.0, 0.0, 0.0, 0.0};
+          }
+          if (last) {
+            // D = R^T K^T: lane l, register q holds Q[16 ti + (l & 15)][16 tj + dr], dr = (l >> 4) + 4 q
+            const int tj = inA ? tA : tB;
+#pragma unroll
+            for (int h = 0; h < RT; ++h) {
+              if (ti0 + h < RTall) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                  const int dr = mfma_drow<double>(lane, q);
+                  qout[frag_index(ti0 + h, 4 * tj + (dr >> 2), (lane & 15) | ((dr & 3) << 4), KB)] = sum[h][q];
+                }
+              }
+              sum[h] = d4{0.0, 0.0, 0.0, 0.0};
+            }
+          }
+        }
+      }
+    };
+    for (int s0 = 0; s0 < ES; s0 += 2 * XT_U) {
+      if (s0 + XT_U < ES) load_batch(r1, s0 + XT_U);
+      run_batch(r0, s0);
+      if (s0 + XT_U < ES) {
+        if (s0 + 2 * XT_U < ES) load_batch(r0, s0 + 2 * XT_U);
+        run_batch(r1, s0 + XT_U);
+      }
+    }
+  }
+  KST(st, 5);
+  KST_END(st);
+}
+
+// ---------------------------------------------------------------------------
 // cross_big32 (DKG_PLAN_F32 with the K(x, X) fill): cross_big_body's 64 x 32 blocks on v_mfma_f32_16x16x4_f32,
 // R^T and K(x, X) quad-packed in fp32 (Plan::root32, Plan::kx32 written by the fill), Q_X written quad-packed
 // (Plan::q32, the covariance stage's A operand).  Column tile tj needs the words j < tj + 1 (k-blocks

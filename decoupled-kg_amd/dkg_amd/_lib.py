@@ -107,6 +107,9 @@ SIGNATURES = {
     "dkg_debug_read_kstamps": (c_int, [c_void_p, c_int]),
     "dkg_debug_wave_ops": (c_int, [c_void_p, c_void_p, c_void_p]),
     "dkg_debug_cov_kernels": (c_int, [c_int]),
+    "dkg_debug_cross_tall": (c_int, [c_int]),
+    "dkg_debug_cross_tall_launches": (ctypes.c_longlong, []),
+    "dkg_debug_cross_tall_eligible": (c_int, [c_int, c_int, c_int, c_int]),
     "dkg_debug_mfma_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 

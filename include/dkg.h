@@ -363,6 +363,20 @@ int dkg_debug_mfma_f64(const double* a, const double* b, double* c, void* stream
 #define DKG_COV_ENABLE_REG 4  /* register-operand blocks, any m, one 8-wave workgroup per CU */
 int dkg_debug_cov_kernels(int mask);
 
+/* The cross stage's one-launch kernel with K(x, X) kept in LDS (cross_tall_kernel; fp64 plans, every output's
+ * n_pad <= 256).  mode -1: the default dispatch (launches of at least 512 candidates, which would otherwise fill
+ * K(x, X) with a kernel of its own), 0: never, 1: every eligible shape whatever the candidate count (tests and
+ * A/B measurements; initially from the environment variable DKG_CROSS_TALL).  Same bits either way.  Returns the
+ * previous mode; any other value of mode is an error (returns -2, dkg_last_error) and changes nothing.  The mode is
+ * read when a launch is issued: graphs captured earlier keep the kernels they were captured with. */
+int dkg_debug_cross_tall(int mode);
+/* Launches issued (or captured) through the one-launch cross kernel since the library was loaded. */
+long long dkg_debug_cross_tall_launches(void);
+/* 1 when a forward launch over B candidates of a plan with widest padded n `max_n_pad` (a multiple of 16), input
+ * dimension d and fp32 contractions or not (f32) takes the one-launch cross kernel under the current mode, else 0;
+ * -2 on bad arguments.  Host only: no device is touched. */
+int dkg_debug_cross_tall_eligible(int max_n_pad, int d, int B, int f32);
+
 /* ---- Launcher: captured forward graphs of several streams enqueued side by side from host threads.
  * A hipGraphLaunch costs ~1 us of host time per kernel node plus ~9 us; one thread launching every
  * stream's graphs in turn leaves the last stream idle for the others' launches.  The
