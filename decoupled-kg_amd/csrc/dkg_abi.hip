@@ -828,6 +828,19 @@ int dkg_debug_cross_tall_eligible(int max_n_pad, int d, int B, int f32) {
   return cross_tall_eligible(max_n_pad, d, B, f32 != 0) ? 1 : 0;
 }
 
+int dkg_debug_plan_envelope(const void* host_plan, int out[4]) {
+  if (!host_plan || !out) {
+    fail(DKG_ERR_ARG, "dkg_debug_plan_envelope: NULL pointer");
+    return -2;
+  }
+  const Plan& h = *static_cast<const Plan*>(host_plan);
+  out[0] = h.stream ? 0 : env_slots(h.N + 1);
+  out[1] = h.stream ? 1 : 0;
+  out[2] = h.sw;
+  out[3] = h.split;
+  return 0;
+}
+
 int dkg_debug_wave_ops(const double* in, double* out, void* stream) {
   if (!in || !out) return fail(DKG_ERR_ARG, "NULL pointer");
   return hip_check(launch_debug_wave(in, out, (hipStream_t)stream), "debug_wave_kernel");

@@ -2189,11 +2189,12 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // kernel-derivative terms: lane h handles queued line h
-        {
-          const bool act = lane < nh;
-          const int k = act ? hk[lane] : 1;
-          const double Dw = act ? hD[lane] : 0.0;
+        // kernel-derivative terms: lane h handles queued lines h, h + 64, ... (the queue holds up to HCAP = 128
+        // lines, two per lane; one round when it holds at most 64: the bits of a one-round flush)
+        for (int h0 = 0; h0 < nh; h0 += 64) {
+          const bool act = h0 + lane < nh;
+          const int k = act ? hk[h0 + lane] : 1;
+          const double Dw = act ? hD[h0 + lane] : 0.0;
           const double* z = disc + (size_t)(k - 1) * d;
           double hc[M];
 #pragma unroll

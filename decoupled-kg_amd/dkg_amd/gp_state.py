@@ -348,6 +348,15 @@ class ForwardPlan:
         self._fwd_grad_hostx = lib.dkg_plan_forward_grad_hostx
         self._dev_ptr = _lib.ptr(self.dev)
 
+    def envelope_geometry(self) -> dict:
+        """Which envelope kernel the plan launches (dkg_debug_plan_envelope; host only): ``slots`` (register
+        slots per lane of the staged envelope, 2 / 8 / 17 / 33; 0 when streaming), ``stream`` (1: the lines are
+        streamed from global memory), ``sw`` (waves per workgroup) and ``split`` (workgroups per candidate)."""
+        out = (ctypes.c_int * 4)()
+        if _lib.load().dkg_debug_plan_envelope(self.host, out) != 0:
+            _lib.check(_lib.DKG_ERR_ARG, "dkg_debug_plan_envelope")
+        return {"slots": out[0], "stream": out[1], "sw": out[2], "split": out[3]}
+
     def status(self, reset: bool = False) -> int:
         """The bits of the fused launches' in-launch waits that gave up since the last reset (0: every hand-off
         matched; dkg_plan_status); synchronises the plan's stream."""

@@ -377,6 +377,12 @@ long long dkg_debug_cross_tall_launches(void);
  * -2 on bad arguments.  Host only: no device is touched. */
 int dkg_debug_cross_tall_eligible(int max_n_pad, int d, int B, int f32);
 
+/* Which envelope kernel an initialised plan launches (decided by the LDS arithmetic of dkg_plan_init):
+ * out = {register slots per lane of the staged envelope (2, 8, 17 or 33; 0 when the plan streams its lines),
+ * 1 if it streams them from global memory else 0, waves per workgroup, workgroups per candidate}.  Returns 0, or
+ * -2 when host_plan or out is NULL (dkg_last_error).  Host only: no device is touched. */
+int dkg_debug_plan_envelope(const void* host_plan, int out[4]);
+
 /* ---- Launcher: captured forward graphs of several streams enqueued side by side from host threads.
  * A hipGraphLaunch costs ~1 us of host time per kernel node plus ~9 us; one thread launching every
  * stream's graphs in turn leaves the last stream idle for the others' launches.  The

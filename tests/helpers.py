@@ -154,6 +154,113 @@ def check_parity_case(res):
           f"{res['line_floor_max']:.3g} (diagnostic, not asserted)")
 
 
+FAMILIES = {"M12": ("matern", 0.5), "M32": ("matern", 1.5), "M52": ("matern", 2.5), "RBF": ("rbf", None)}
+ALL_FAMILIES = ("M52", "M32", "M12", "RBF")
+
+
+def grad_case(m, d, ns, families, N, S, B, seed, lengthscale=None, noise=None, grid=False, mean_shift=0.0):
+    """A seeded value+gradient problem from plain tensors (no device, no global RNG): the same inputs on the
+    CPU oracle and on the GPU.  -> (ModelListGPState, D [N, d], W [S, m], X [B, d]).
+
+    Output i: train_x = rand(n_i, d); y = sin(3 sum(x) / sqrt(d) + i) + 0.1 randn; one lengthscale per
+    dimension (0.5 + 0.5 rand(d)) sqrt(d / 2), all different (a scalar ``lengthscale`` overrides it);
+    outputscale 1 + 0.5 i; noise 1e-2 (1 + i) (a scalar ``noise`` overrides it); mean_constant 0.1 i - 0.2
+    (+ ``mean_shift``);
+    y_mean 0.3 i; y_std 1 + 0.25 i; the kernel family cycles over ``families`` (keys of FAMILIES).
+    D = rand(N, d), or linspace(0, 1, N) with ``grid`` (d = 1); W = rand(S, m) + 0.05 with rows summing to 1;
+    X = rand(B, d).  ``ns``: one n per output (cycled when shorter than m)."""
+    from dkg_amd.model import ModelListGPState, SingleTaskGPState
+
+    g = torch.Generator().manual_seed(int(seed))
+    rand = lambda *s: torch.rand(*s, generator=g, dtype=torch.double)  # noqa: E731
+    models = []
+    for i in range(m):
+        n = ns[i % len(ns)]
+        x = rand(n, d)
+        y = torch.sin(3.0 * x.sum(-1) / math.sqrt(d) + i) + 0.1 * torch.randn(n, generator=g, dtype=torch.double)
+        ls = (0.5 + 0.5 * rand(d)) * math.sqrt(d / 2.0)
+        if lengthscale is not None:
+            ls = torch.full((d,), float(lengthscale), dtype=torch.double)
+        kind, nu = FAMILIES[families[i % len(families)]]
+        models.append(SingleTaskGPState(x, y, ls, 1.0 + 0.5 * i, 1e-2 * (1 + i) if noise is None else float(noise),
+                                        0.1 * i - 0.2 + mean_shift, kind, 2.5 if nu is None else nu, 0.3 * i, 1.0 + 0.25 * i))
+    if grid:
+        assert d == 1
+        D = torch.linspace(0.0, 1.0, N, dtype=torch.double).reshape(N, 1)
+    else:
+        D = rand(N, d)
+    W = rand(S, m) + 0.05
+    W = W / W.sum(-1, keepdim=True)
+    X = rand(B, d)
+    return ModelListGPState(*models), D, W, X
+
+
+def _row(id, m, d, ns, fam, N, S, B, targets, slots, split=1, stream=0, seed=0, **kw):
+    return dict(id=id, m=m, d=d, ns=ns, fam=fam, N=N, S=S, B=B, targets=targets, slots=slots, split=split,
+                stream=stream, seed=seed, kw=kw)
+
+
+# The value+gradient case matrix (tests/test_gpu_grad_matrix.py on the device, tests/test_grad_matrix_oracle.py
+# on the reference alone).  slots / stream / split: the envelope instantiation the row is there for
+# (ForwardPlan.envelope_geometry): 2 / 8 / 17 / 33 register slots by N + 1 <= 128 / 512 / 1088 / 2112, streaming
+# above that or when the gradient envelope's LDS exceeds 160 KiB; split = ceil(S / 8) workgroups per candidate.
+GRAD_MATRIX = [
+    # each kernel family alone, one lengthscale per dimension
+    *[_row(f"family-{f}", 2, 3, (40, 40), (f,), 200, 8, 19, (None, 1), 8, seed=sd)
+      for f, sd in zip(ALL_FAMILIES, (1, 12, 13, 14))],
+    # output buckets M = 1, 3, 4, 8 (m = 5 pads the M = 8 records with zero components)
+    _row("M1", 1, 2, (37,), ("M52",), 100, 1, 19, (None,), 2, seed=3),
+    _row("M3-mixed", 3, 3, (37, 50, 23), ALL_FAMILIES, 150, 8, 19, (None, 2), 8, seed=22),
+    _row("M4", 4, 4, (33, 48, 17, 64), ALL_FAMILIES, 150, 8, 19, (None, 0), 8, seed=5),
+    _row("M8-padded-m5", 5, 2, (20, 31, 16, 45, 27), ALL_FAMILIES, 120, 8, 19, (None, 4), 2, seed=24),
+    _row("M8-full", 8, 2, (20, 31, 16, 45, 27, 38, 18, 52), ALL_FAMILIES, 120, 8, 19, (None, 7), 2, seed=25),
+    # dimension buckets DM = 2, 4, 8, 16 and their edges
+    _row("d1", 2, 1, (25, 25), ("M52", "M32"), 60, 8, 19, (None, 0), 2, seed=31),
+    *[_row(f"d{d}", 2, d, (64, 64), ("M52", "M32"), 200, 8, 19, (None, 0), 8, seed=sd)
+      for d, sd in ((4, 3), (5, 4), (8, 8), (9, 40), (16, 47))],
+    # more than two workgroups per candidate: ordered last-arriver sums
+    _row("S24", 2, 3, (40, 40), ("M52", "M32"), 200, 24, 19, (None, 1), 8, split=3, seed=51),
+    _row("S40-m3", 3, 3, (40, 40, 40), ("M52", "M32", "M12"), 200, 40, 19, (None, 1), 8, split=5, seed=52),
+    # envelope instantiations
+    _row("slots2-B1", 2, 2, (16, 17), ("M52", "RBF"), 9, 3, 1, (None,), 2, seed=2),
+    _row("slots33", 2, 3, (40, 40), ("M52", "M32"), 1100, 8, 19, (None,), 33, seed=62),
+    _row("stream-by-N", 2, 3, (40, 40), ("M52", "M32"), 2200, 8, 19, (None, 1), 0, stream=1, seed=63),
+    # the gradient envelope's LDS (M d stage_len(n_pad) doubles of J rows) over 160 KiB at a small N: the forward
+    # plan of the same model is staged (8 slots), the gradient plan streams
+    _row("stream-by-LDS", 5, 6, (16, 20, 31, 25, 18), ALL_FAMILIES, 130, 8, 19, (None,), 0, stream=1, seed=64),
+    _row("stream-by-LDS-m3", 3, 12, (160, 60, 90), ALL_FAMILIES, 130, 8, 19, (None, 0), 0, stream=1, seed=65),
+    # n_pad > 256: the flush's second body
+    _row("np272", 2, 3, (260, 40), ("M52", "RBF"), 150, 8, 19, (None, 0), 8, seed=32),
+    # long envelopes (more lines than the flush queue's 128, more survivors than the hull's 125)
+    _row("long-M12-m1", 1, 1, (6,), ("M12",), 1000, 3, 9, (None,), 17, seed=81, lengthscale=1.0, noise=0.1,
+         grid=True, mean_shift=1.2),
+    _row("long-M12-m2", 2, 1, (6, 6), ("M12",), 1000, 3, 9, (None,), 17, seed=3, lengthscale=1.0, noise=0.1,
+         grid=True),
+    _row("long-M32-m1", 1, 1, (12,), ("M32",), 1000, 3, 9, (None,), 17, seed=83, lengthscale=0.3, noise=1e-2,
+         grid=True),
+    _row("long-M32-m2", 2, 1, (12, 12), ("M32",), 1000, 3, 9, (None,), 17, seed=84, lengthscale=0.3, noise=1e-2,
+         grid=True),
+]
+GRAD_ROWS = {r["id"]: r for r in GRAD_MATRIX}
+GRAD_CASES = [(r["id"], t) for r in GRAD_MATRIX for t in r["targets"]]
+
+
+def grad_row_problem(row, B=None):
+    """grad_case of a GRAD_MATRIX row (``B`` overrides the row's candidate count)."""
+    return grad_case(row["m"], row["d"], row["ns"], row["fam"], row["N"], row["S"], row["B"] if B is None else B,
+                     row["seed"], **row["kw"])
+
+
+def oracle_value_and_grad(om, X, D, W, target):
+    """KG [B] and dKG/dX [B, d] of the batched oracle by torch.autograd."""
+    from oracle.discretekg import discrete_kg_batched
+
+    Xr = X.clone().requires_grad_(True)
+    kg, _ = discrete_kg_batched(om, Xr, D, W, target)
+    (g,) = torch.autograd.grad(kg.sum(), Xr)
+    return kg.detach(), g
+
+
 def load_golden(name: str):
     """tests/golden/<name>.npz -> (state, oracle ModelList, D, W, X, arrays dict)."""
     import os
