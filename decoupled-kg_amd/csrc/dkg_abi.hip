@@ -484,6 +484,113 @@ int dkg_prepare_outputs(const dkg_output* outs, int m, int d, const double* cons
   return DKG_OK;
 }
 
+// Workspace of dkg_mll_value_grad: a head shared by the outputs (their factorisation flags, then their result rows
+// [DKG_MAX_OUTPUTS][MLL_OUT]: one copy each way), then per output the pieces below (offsets from the output's
+// base, 256-byte aligned).
+constexpr size_t MLL_WS_OUT = 256;
+constexpr size_t MLL_WS_HEAD = MLL_WS_OUT + ((DKG_MAX_OUTPUTS * MLL_OUT * sizeof(double) + 255) & ~(size_t)255);
+struct MllCarve {
+  size_t A, X, alpha, part, total;
+};
+static MllCarve mll_carve(int n) {
+  MllCarve c{};
+  const size_t nn = align256((size_t)n * n * sizeof(double));
+  c.A = 0;
+  c.X = nn;
+  c.alpha = c.X + nn;
+  c.part = c.alpha + align256((size_t)pad16(n) * sizeof(double));
+  c.total = c.part + align256((size_t)mll_tiles(n) * MLL_NP * sizeof(double));
+  return c;
+}
+
+size_t dkg_mll_workspace(const int* n, int m) {
+  if (!n || m < 1 || m > DKG_MAX_OUTPUTS) return 0;
+  size_t total = MLL_WS_HEAD;
+  for (int i = 0; i < m; ++i) {
+    if (n[i] < 1 || n[i] > 1024) return 0;
+    total += mll_carve(n[i]).total;
+  }
+  return total;
+}
+
+int dkg_mll_value_grad(const dkg_output* outs, int m, int d, const double* const* train_y, int max_tries, void* work,
+                       size_t work_bytes, double* value, double* grad, double* jitter_used, void* stream) {
+  if (!outs || !train_y || !work || !value || !grad) return fail(DKG_ERR_ARG, "NULL pointer");
+  if (m < 1) return fail(DKG_ERR_ARG, "m=%d outputs", m);
+  if (m > DKG_MAX_OUTPUTS) return fail(DKG_ERR_UNSUPPORTED, "m=%d outputs (supported 1..%d)", m, DKG_MAX_OUTPUTS);
+  if (d < 1) return fail(DKG_ERR_ARG, "d=%d", d);
+  if (d > DKG_MAX_DIM) return fail(DKG_ERR_UNSUPPORTED, "d=%d (supported 1..%d)", d, DKG_MAX_DIM);
+  if (max_tries < 0) return fail(DKG_ERR_ARG, "max_tries=%d", max_tries);
+  int ns[DKG_MAX_OUTPUTS];
+  for (int i = 0; i < m; ++i) {
+    const dkg_output& o = outs[i];
+    if (!train_y[i] || !o.inv_lengthscale || !o.train_x) return fail(DKG_ERR_ARG, "NULL pointer");
+    if (o.n < 1) return fail(DKG_ERR_ARG, "n=%d training points", o.n);
+    if (o.n > 1024) return fail(DKG_ERR_UNSUPPORTED, "n=%d > 1024 training points", o.n);
+    if (o.kernel < DKG_MATERN12 || o.kernel > DKG_RBF) return fail(DKG_ERR_ARG, "kernel id %d", o.kernel);
+    ns[i] = o.n;
+  }
+  const size_t need = dkg_mll_workspace(ns, m);
+  if (work_bytes < need) return fail(DKG_ERR_WORKSPACE, "workspace %zu bytes < required %zu", work_bytes, need);
+  hipStream_t s = (hipStream_t)stream;
+  PrepBatch b{};
+  MllBatch mb{};
+  mb.d = d;
+  int st, h_info[DKG_MAX_OUTPUTS];
+  double jit[DKG_MAX_OUTPUTS];
+  char* base = static_cast<char*>(work);
+  int* d_info = reinterpret_cast<int*>(base);
+  double* d_out = reinterpret_cast<double*>(base + MLL_WS_OUT);
+  base += MLL_WS_HEAD;
+  if ((st = hip_check(hipMemsetAsync(d_info, 0, DKG_MAX_OUTPUTS * sizeof(int), s), "hipMemsetAsync"))) return st;
+  for (int i = 0; i < m; ++i) {
+    const MllCarve c = mll_carve(ns[i]);
+    b.A[i] = reinterpret_cast<double*>(base + c.A);
+    b.X[i] = reinterpret_cast<double*>(base + c.X);
+    b.n[i] = ns[i];
+    b.info[i] = d_info + i;
+    mb.o[i] = outs[i];
+    mb.y[i] = train_y[i];
+    mb.L[i] = b.A[i];
+    mb.M[i] = b.X[i];
+    mb.alpha[i] = reinterpret_cast<double*>(base + c.alpha);
+    mb.info[i] = b.info[i];
+    mb.part[i] = reinterpret_cast<double*>(base + c.part);
+    mb.out[i] = d_out + (size_t)i * MLL_OUT;
+    base += c.total;
+    jit[i] = 0.0;
+    if ((st = hip_check(launch_kernel_matrix(outs[i], d, outs[i].train_x, ns[i], outs[i].train_x, ns[i],
+                                             outs[i].noise, b.A[i], s), "kernel_matrix")))
+      return st;
+  }
+  // the factorisation as dkg_prepare_outputs runs it: every output's first attempt in one chain of launches and
+  // one status check, the outputs that failed retried with jitter one by one
+  if ((st = hip_check(launch_cholesky_batch(b, m, s), "cholesky_batch"))) return st;
+  if ((st = hip_check(hipMemcpyAsync(h_info, d_info, m * sizeof(int), hipMemcpyDeviceToHost, s), "hipMemcpyAsync")) ||
+      (st = hip_check(hipStreamSynchronize(s), "hipStreamSynchronize")))
+    return st;
+  for (int i = 0; i < m; ++i)
+    if (h_info[i] != 0 && (st = cholesky_attempts(&outs[i], d, b.A[i], b.X[i], b.info[i], 1, max_tries, s, &jit[i])))
+      return st;
+  if ((st = hip_check(launch_tri_inverse_batch(b, m, s), "tri_inverse_batch"))) return st;
+  for (int i = 0; i < m; ++i)
+    if ((st = hip_check(launch_alpha(b.X[i], train_y[i], outs[i].mean_constant, ns[i],
+                                     const_cast<double*>(mb.alpha[i]), b.info[i], s), "alpha")))
+      return st;
+  if ((st = hip_check(launch_mll(mb, m, s), "mll"))) return st;
+  double h_out[DKG_MAX_OUTPUTS][MLL_OUT];
+  if ((st = hip_check(hipMemcpyAsync(h_out, d_out, (size_t)m * MLL_OUT * sizeof(double), hipMemcpyDeviceToHost, s),
+                      "hipMemcpyAsync")) ||
+      (st = hip_check(hipStreamSynchronize(s), "hipStreamSynchronize")))
+    return st;
+  for (int i = 0; i < m; ++i) {
+    value[i] = h_out[i][0];
+    for (int j = 0; j < d + 3; ++j) grad[(size_t)i * (d + 3) + j] = h_out[i][1 + j];
+    if (jitter_used) jitter_used[i] = jit[i];
+  }
+  return DKG_OK;
+}
+
 int dkg_kernel_matrix(const dkg_output* o, int d, const double* x1, int n1, const double* x2, int n2,
                       double diag_add, double* out, void* stream) {
   if (!o || !x1 || !x2 || !out || !o->inv_lengthscale) return fail(DKG_ERR_ARG, "NULL pointer");

@@ -32,6 +32,14 @@ constexpr int WAVE = 64;
 
 __host__ __device__ inline int pad16(int x) { return (x + 15) & ~15; }
 
+// Lower tile (ti, tj), tj <= ti, of the row-major enumeration t = ti (ti + 1) / 2 + tj.
+__device__ __forceinline__ void lower_tile(int t, int& ti, int& tj) {
+  ti = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
+  while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
+  while (ti * (ti + 1) / 2 > t) --ti;
+  tj = t - ti * (ti + 1) / 2;
+}
+
 // All output states by value (kernel argument, < 1 KiB).
 struct Outputs {
   dkg_output o[DKG_MAX_OUTPUTS];

@@ -164,6 +164,28 @@ struct AppendArgs {
 constexpr size_t APPEND_WS_LAM = 64, APPEND_WS_L = 256, APPEND_WS_BETA = 256 + 8192, APPEND_WS_BYTES = 256 + 16384;
 // The copy, solve, pack and discretisation launches of one append (root_frag: the new R^T, from Mn).
 hipError_t launch_append(const AppendArgs& a, double* root_frag, hipStream_t s);
+// Marginal log-likelihood and its gradient (dkg_mll.hip, dkg_mll_value_grad): after the factorisation, inverse
+// and alpha of every output.  part: [mll_tiles(n)][MLL_NP] tile partials; out: [MLL_OUT] = value, then the
+// gradient [c, l_1 .. l_d, s, noise].
+constexpr int MLL_TB = 32;                    // tile width of the pair space
+constexpr int MLL_NP = DKG_MAX_DIM + 2;       // partials per tile: tr W, sum W kappa, sum W h t_j^2 (j < d)
+constexpr int MLL_OUT = DKG_MAX_DIM + 4;      // value + d + 3 gradient entries (stride of the result rows)
+__host__ __device__ inline int mll_tiles(int n) {
+  const int nt = (n + MLL_TB - 1) / MLL_TB;
+  return nt * (nt + 1) / 2;
+}
+struct MllBatch {
+  dkg_output o[DKG_MAX_OUTPUTS];             // n, kernel, hyperparameters, inv_lengthscale, train_x
+  const double* y[DKG_MAX_OUTPUTS];          // targets [n]
+  const double* L[DKG_MAX_OUTPUTS];          // chol(K), row-major n x n
+  const double* M[DKG_MAX_OUTPUTS];          // L^{-1}, row-major n x n, zero upper triangle
+  const double* alpha[DKG_MAX_OUTPUTS];      // K^{-1} (y - c) [pad16(n)]
+  const int* info[DKG_MAX_OUTPUTS];          // the factorisation's status (non-zero: the output is skipped)
+  double* part[DKG_MAX_OUTPUTS];
+  double* out[DKG_MAX_OUTPUTS];
+  int d;
+};
+hipError_t launch_mll(const MllBatch& b, int m, hipStream_t s);
 // fp32 quad-packed copy (frag32_index) of a pair-packed fp64 (rows x n) matrix.
 hipError_t launch_frag_to_f32(const double* frag, int rows, int n, float* out, hipStream_t s);
 // The plan's per-scalarisation intercepts and their maxima (Plan::icpt / itop / itopk), from mu_all.

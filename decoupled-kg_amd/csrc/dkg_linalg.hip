@@ -29,14 +29,6 @@ constexpr int LB = 32;  // block width
 #define DKG_CHOL_EXACT_PIVOT 1
 #endif
 
-// Lower tile (ti, tj), tj <= ti, of the row-major enumeration t = ti (ti + 1) / 2 + tj.
-__device__ __forceinline__ void lower_tile(int t, int& ti, int& tj) {
-  ti = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
-  while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
-  while (ti * (ti + 1) / 2 > t) --ti;
-  tj = t - ti * (ti + 1) / 2;
-}
-
 // ---------------------------------------------------------------------------
 // The diagonal block kb of one output, updated and held in LDS (sC, lower triangle valid): factor it
 // (L_kk), invert it (W_kk = L_kk^{-1}), store L_kk into A's lower block (the block's upper part zeroed)

@@ -72,6 +72,9 @@ SIGNATURES = {
     "dkg_append_observation": (c_int, [POINTER(DkgOutput), c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                        c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dkg_mll_workspace": (c_size_t, [POINTER(c_int), c_int]),
+    "dkg_mll_value_grad": (c_int, [POINTER(DkgOutput), c_int, c_int, POINTER(c_void_p), c_int, c_void_p, c_size_t,
+                                   POINTER(c_double), POINTER(c_double), POINTER(c_double), c_void_p]),
     "dkg_forward_workspace": (c_size_t, [POINTER(DkgOutput), c_int, c_int, c_int, c_int]),
     "dkg_forward": (c_int, [POINTER(DkgOutput), c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                             c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -150,6 +153,16 @@ def check(status: int, what: str) -> None:
     if status == DKG_ERR_NOT_PD:
         raise NotPSDError(msg)
     raise DkgNativeError(msg)
+
+
+def check_fit(status: int, what: str) -> None:
+    """``check`` for the fit's objective (dkg_mll_value_grad): a covariance that is not positive definite after
+    the jitter retries raises the ``torch.linalg.LinAlgError`` the host objective's ``fit._chol`` raises."""
+    if status == DKG_ERR_NOT_PD:
+        import torch
+
+        raise torch.linalg.LinAlgError(f"{what}: {load().dkg_last_error().decode(errors='replace')}")
+    check(status, what)
 
 
 def ptr(t) -> int:

@@ -108,22 +108,34 @@ def surrogate(train_x: Sequence[Tensor], train_y: Sequence[Tensor], hyper: Dict[
     return ModelListGPState(*outs)
 
 
-def fit_hyperparameters(problem: "GPProblem", model_config: dict, n: int = 1000) -> Dict[str, list]:
+def fit_hyperparameters(problem: "GPProblem", model_config: dict, n: int = 1000,
+                        fit_on_device: bool = False) -> Dict[str, list]:
     """``bo_loop.fit_hyperparameters`` (``:63-79``): n Sobol points of the problem (global RNG, as
     ``draw_sobol_samples`` without a seed), every objective evaluated there, the MAP fit of the surrogate
-    (``dkg_amd.fit.fit_map``)."""
+    (``dkg_amd.fit.fit_map``).  ``fit_on_device``: the fit's objective is evaluated on ``problem.device``
+    (``fit_map(device=...)``; see ``run_mobo``)."""
     from .fit import fit_map
 
     x = draw_sobol_samples(problem.bounds, n, 1).squeeze(-2)
     y = problem(x)
-    return fit_map([x] * problem.num_objectives, [y[:, i] for i in range(problem.num_objectives)], model_config)
+    return fit_map([x] * problem.num_objectives, [y[:, i] for i in range(problem.num_objectives)], model_config,
+                   device=_fit_device(problem, fit_on_device))
+
+
+def _fit_device(problem: "GPProblem", fit_on_device: bool):
+    if not fit_on_device:
+        return None
+    if problem.device is None:
+        raise ValueError("fit_on_device needs a problem on a ROCm device")
+    return problem.device
 
 
 def run_mobo(problem: GPProblem, hyper: Dict[str, Sequence[float]], separate: bool, n_iter: int = 2,
              n_init: int = 6, costs: Sequence[float] = (1, 10), n_scalarisations: int = 16,
              spec: Optional[DiscreteKgOptimisationSpec] = None, seed: int = 0,
              catalog: Optional[DataCatalog] = None, run_key: Optional[str] = None,
-             fit_hyperparams: str = "never", incremental: bool = False) -> Dict[str, List]:
+             fit_hyperparams: str = "never", incremental: bool = False,
+             fit_on_device: bool = False) -> Dict[str, List]:
     """``bo_loop.run_mobo`` with the discrete-KG strategy for ``n_iter`` BO steps; returns the
     query history (x, objective index or None for full evaluation, observed values, acquisition).
     With ``catalog`` it also writes the reference's checkpoints and query-history table under
@@ -133,21 +145,27 @@ def run_mobo(problem: GPProblem, hyper: Dict[str, Sequence[float]], separate: bo
     fit's (``:600-614``).  ``incremental`` (``never`` / ``once`` only: with ``always`` the hyperparameters change
     at every step and it is ignored) turns ``set_incremental_state`` on for the run, so each step's device
     state comes from the previous one by appending the new observations instead of a full rebuild; the
-    switch is restored afterwards."""
+    switch is restored afterwards.  ``fit_on_device`` (``always`` only; off by default): every refit evaluates
+    its objective on ``problem.device`` (``fit_map(device=...)``, one ``dkg_mll_value_grad`` call per
+    evaluation) instead of on the host with autograd.  Measured crossover (m = 2, d = 2): none down
+    to n = 10 -- a device evaluation costs its launches and two synchronisations whatever n is, 0.24 ms there,
+    against the host's 0.87 ms; 2.5 against 62 ms at n = 1000.  Opt-in all the same: the two routes take the scaled
+    distances differently, so their fits agree to the optimiser's tolerance, not bit for bit, and
+    the default keeps the host route's results."""
     if fit_hyperparams not in ("never", "once", "always"):
         raise ValueError(f"Unexpected value for fit_hyperparams. Got {fit_hyperparams!r}")
     on = incremental and fit_hyperparams != "always"
     prev = set_incremental_state(True) if on else None
     try:
         return _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations, spec, seed, catalog,
-                         run_key, fit_hyperparams)
+                         run_key, fit_hyperparams, _fit_device(problem, fit_on_device and fit_hyperparams == "always"))
     finally:
         if on:
             set_incremental_state(prev)
 
 
 def _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations, spec, seed, catalog, run_key,
-              fit_hyperparams) -> Dict[str, List]:
+              fit_hyperparams, fit_device=None) -> Dict[str, List]:
     m, d = problem.num_objectives, problem.gp.input_dim
     # the pipeline's --seed (main.py:235, utils.set_random_seed): every later draw comes from the global RNG, as
     # in the reference -- the initial Sobol points (generate_initial_data, bo_loop.py:48-49: no seed), each
@@ -180,7 +198,8 @@ def _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations,
         if fit_hyperparams == "always":
             from .fit import fit_map
 
-            hyper = fit_map(train_x, train_y, model_config, fixed_means=None if first else fitted_means)
+            hyper = fit_map(train_x, train_y, model_config, fixed_means=None if first else fitted_means,
+                            device=fit_device)
             if first:
                 fitted_means = list(hyper["means"])
         return surrogate(train_x, train_y, hyper)
@@ -237,22 +256,25 @@ def _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations,
 
 def run_smoke(problem: GPProblem, hyper: Dict[str, Sequence[float]], seed: int = 0,
               catalog: Optional[DataCatalog] = None, fit_hyperparams: str = "never",
-              incremental: bool = False) -> Dict[str, Dict]:
+              incremental: bool = False, fit_on_device: bool = False) -> Dict[str, Dict]:
     """``run_pipeline`` under ``SMOKE_TEST`` (``main.py:171-216``): the separate-evaluation run and
     the full-evaluation run, two BO steps each; with ``catalog`` both write the reference's files.
     ``fit_hyperparams = "once"`` fits the hyperparameters first (``main.py:181-182``, saved to the catalog's
     ``hyperparameters.pt`` as the fitted surrogate's state dict) and both runs use them; ``"always"`` refits
-    inside the runs.  ``incremental``: as ``run_mobo``'s."""
+    inside the runs.  ``incremental``, ``fit_on_device``: as ``run_mobo``'s (``fit_on_device`` also moves the
+    ``once`` fit's objective to the device)."""
     if fit_hyperparams == "once":
         torch.manual_seed(seed)
         cfg = reference_model_config(problem.num_objectives, problem.bounds, "once")
-        hyper = fit_hyperparameters(problem, cfg)
+        hyper = fit_hyperparameters(problem, cfg, fit_on_device=fit_on_device)
         if catalog is not None:
             x = torch.zeros(1, problem.gp.input_dim, dtype=torch.double)
             y = torch.zeros(1, dtype=torch.double)
             catalog.save_model_hyperparameters(
                 to_state_dict(surrogate([x] * problem.num_objectives, [y] * problem.num_objectives, hyper), cfg))
     return {"separate": run_mobo(problem, hyper, separate=True, seed=seed, catalog=catalog,
-                                 fit_hyperparams=fit_hyperparams, incremental=incremental),
+                                 fit_hyperparams=fit_hyperparams, incremental=incremental,
+                                 fit_on_device=fit_on_device),
             "full": run_mobo(problem, hyper, separate=False, seed=seed, catalog=catalog,
-                             fit_hyperparams=fit_hyperparams, incremental=incremental)}
+                             fit_hyperparams=fit_hyperparams, incremental=incremental,
+                             fit_on_device=fit_on_device)}

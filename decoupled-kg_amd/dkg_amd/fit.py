@@ -25,6 +25,7 @@ against central differences, and recovery of known hyperparameters.
 
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Dict, List, Optional, Sequence
 
@@ -138,13 +139,179 @@ class _Output:
         return (logp + lp) / self.n
 
 
+class DeviceMll:
+    """The data of every output and the workspace of ``dkg_mll_value_grad`` on a ROCm device, uploaded once;
+    ``evaluate`` then costs one small host-to-device copy (the inverse lengthscales) and one library call."""
+
+    def __init__(self, train_x: Sequence[Tensor], train_y: Sequence[Tensor], nus: Sequence[float], device):
+        from . import _lib
+
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"the device objective needs a ROCm device. Got {device!r}.")
+        self.m = len(train_x)
+        X = [torch.as_tensor(x, dtype=torch.double).reshape(len(x), -1) for x in train_x]
+        self.d = int(X[0].shape[1])
+        if any(int(x.shape[1]) != self.d for x in X):
+            raise ValueError("every output's train_x must have the same input dimension")
+        self.n = [int(x.shape[0]) for x in X]
+        self.kernel = [3 if math.isinf(nu) else {0.5: 0, 1.5: 1, 2.5: 2}[float(nu)] for nu in nus]
+        y = [torch.as_tensor(t, dtype=torch.double).reshape(-1) for t in train_y]
+        # one upload: every output's inputs, then every output's targets
+        flat = torch.cat([x.reshape(-1) for x in X] + y).to(self.device)
+        self.flat, self.x_ptr, self.y_ptr, off = flat, [], [], 0
+        for n in self.n:
+            self.x_ptr.append(flat.data_ptr() + 8 * off)
+            off += n * self.d
+        for n in self.n:
+            self.y_ptr.append(flat.data_ptr() + 8 * off)
+            off += n
+        self.inv_ls = torch.empty(self.m, self.d, dtype=torch.double, device=self.device)
+        self.inv_ls_host = torch.empty(self.m, self.d, dtype=torch.double).pin_memory()
+        ns = (ctypes.c_int * self.m)(*self.n)
+        self.work_bytes = int(self.lib.dkg_mll_workspace(ns, self.m))
+        if self.work_bytes == 0:
+            from .errors import UnsupportedError
+
+            raise UnsupportedError(f"dkg_mll_workspace: m={self.m}, n={self.n} outside the supported sizes "
+                                   f"(1..8 outputs of 1..1024 training points)")
+        self.work = torch.empty(self.work_bytes, dtype=torch.uint8, device=self.device)
+        self.outs = (_lib.DkgOutput * self.m)()
+        for i in range(self.m):
+            o = self.outs[i]
+            o.n, o.kernel, o.y_mean, o.y_std = self.n[i], self.kernel[i], 0.0, 1.0
+            o.train_x = self.x_ptr[i]
+            o.inv_lengthscale = self.inv_ls.data_ptr() + 8 * self.d * i
+        self.ys = (ctypes.c_void_p * self.m)(*self.y_ptr)
+        self.value = (ctypes.c_double * self.m)()
+        self.grad = (ctypes.c_double * (self.m * (self.d + 3)))()
+        self.jitter = (ctypes.c_double * self.m)()
+
+    def evaluate(self, means, length_scales, output_scales, noises):
+        """(values [m], gradients [m][d + 3] = [d/dmean, d/dlengthscale_1..d, d/doutputscale, d/dnoise], jitters
+        [m]) at natural-space hyperparameters: log N(y | mean, s kappa + (noise + jitter) I) per output."""
+        from . import _lib
+
+        ls = torch.as_tensor(np.asarray(length_scales, dtype=np.float64)).reshape(self.m, self.d)
+        self.inv_ls_host.copy_(1.0 / ls)
+        for i in range(self.m):
+            o = self.outs[i]
+            o.mean_constant, o.outputscale, o.noise = float(means[i]), float(output_scales[i]), float(noises[i])
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            self.inv_ls.copy_(self.inv_ls_host, non_blocking=True)
+            _lib.check_fit(self.lib.dkg_mll_value_grad(self.outs, self.m, self.d, self.ys, len(JITTERS),
+                                                       self.work.data_ptr(), self.work_bytes, self.value, self.grad,
+                                                       self.jitter, stream.cuda_stream), "dkg_mll_value_grad")
+        return (np.array(self.value, dtype=np.float64),
+                np.array(self.grad, dtype=np.float64).reshape(self.m, self.d + 3),
+                np.array(self.jitter, dtype=np.float64))
+
+
+def _nu_of(cfg: dict) -> float:
+    kern = cfg.get("kernel") or {}
+    return float((kern.get("args") or {}).get("nu", 2.5)) if kern.get("type", "matern") == "matern" else math.inf
+
+
+def mll_value_and_grad(train_x: Sequence[Tensor], train_y: Sequence[Tensor], hyper: Dict[str, Sequence],
+                       model_config: dict, device, return_jitter: bool = False):
+    """The outputs' marginal log-likelihoods log N(y_i | mean_i, s_i kappa_i(X_i, X_i) + noise_i I) at ``hyper``
+    (``means``, ``length_scales`` [m][d], ``output_scales``, ``noises``) and their gradients in those
+    (natural-space) hyperparameters, by one ``dkg_mll_value_grad`` call on ``device`` for all outputs: host
+    arrays ``values`` [m] and ``grads`` [m][d + 3], a row being [mean, lengthscale_1..d, outputscale, noise]
+    (``return_jitter``: also the absolute jitter each factorisation needed).  No priors, no division by n; the
+    kernel family of output i is ``model_config["outputs"][i]["kernel"]``'s.  Raises
+    ``torch.linalg.LinAlgError`` when a covariance is not positive definite after the jitter retries."""
+    ev = DeviceMll(train_x, train_y, [_nu_of(model_config["outputs"][i]) for i in range(len(train_x))], device)
+    v, g, j = ev.evaluate(hyper["means"], hyper["length_scales"], hyper["output_scales"], hyper["noises"])
+    return (v, g, j) if return_jitter else (v, g)
+
+
+def _softplus(x: np.ndarray) -> np.ndarray:
+    """torch.nn.functional.softplus (beta 1, threshold 20) in numpy."""
+    x = np.asarray(x, dtype=np.float64)
+    return np.where(x > 20.0, x, np.log1p(np.exp(np.minimum(x, 20.0))))
+
+
+def _sigmoid(x: np.ndarray) -> np.ndarray:
+    """softplus' derivative (1 above the threshold)."""
+    x = np.asarray(x, dtype=np.float64)
+    return np.where(x > 20.0, 1.0, 1.0 / (1.0 + np.exp(-np.minimum(x, 20.0))))
+
+
+def _gamma_np(x: np.ndarray, prior) -> tuple:
+    """GammaPrior.log_prob summed over x's entries, and its derivative per entry."""
+    a, b = prior
+    x = np.atleast_1d(np.asarray(x, dtype=np.float64))
+    return float((a * math.log(b) - math.lgamma(a) + (a - 1.0) * np.log(x) - b * x).sum()), (a - 1.0) / x - b
+
+
+def _device_objective(outs: "List[_Output]", device):
+    """``fit_map``'s objective with the likelihoods and their gradients from the device (one
+    ``dkg_mll_value_grad`` call per evaluation for all outputs); the Gamma priors, the softplus chain rule, the
+    division by n, shared (non-ARD) lengthscales and fixed means / noises are scalar work done here."""
+    ev = DeviceMll([o.X for o in outs], [o.y for o in outs], [o.nu for o in outs], device)
+
+    def objective(v: np.ndarray):
+        v = np.asarray(v, dtype=np.float64)
+        parts, k = [], 0
+        for o in outs:
+            raw = v[k:k + o.n_raw]
+            j = 0 if o.fixed_mean is not None else 1
+            c = float(o.fixed_mean) if o.fixed_mean is not None else float(raw[0])
+            ls = _softplus(raw[j:j + o.nls])
+            os_ = float(_softplus(raw[j + o.nls]))
+            noise = float(o.noise0) if o.fix_noise else float(raw[j + o.nls + 1])
+            parts.append((o, k, j, c, ls, os_, noise))
+            k += o.n_raw
+        val, grad, _ = ev.evaluate([p[3] for p in parts],
+                                   [np.broadcast_to(p[4], (p[0].d,)) if not p[0].ard else p[4] for p in parts],
+                                   [p[5] for p in parts], [p[6] for p in parts])
+        loss, g = 0.0, np.zeros_like(v)
+        for i, (o, k, j, c, ls, os_, noise) in enumerate(parts):
+            raw = v[k:k + o.n_raw]
+            d = o.d
+            lp = 0.0
+            g_ls = grad[i, 1:1 + d] if o.ard else np.array([grad[i, 1:1 + d].sum()])
+            g_os, g_noise = grad[i, 1 + d], grad[i, 2 + d]
+            if o.ls_prior:
+                p, dp = _gamma_np(ls, o.ls_prior)
+                lp += p
+                g_ls = g_ls + dp
+            if o.os_prior:
+                p, dp = _gamma_np(os_, o.os_prior)
+                lp += p
+                g_os = g_os + dp[0]
+            if o.noise_prior:
+                p, dp = _gamma_np(noise, o.noise_prior)
+                lp += p
+                g_noise = g_noise + dp[0]
+            loss -= (val[i] + lp) / o.n
+            if o.fixed_mean is None:
+                g[k] = -grad[i, 0] / o.n
+            g[k + j:k + j + o.nls] = -g_ls * _sigmoid(raw[j:j + o.nls]) / o.n
+            g[k + j + o.nls] = -g_os * float(_sigmoid(raw[j + o.nls])) / o.n
+            if not o.fix_noise:
+                g[k + j + o.nls + 1] = -g_noise / o.n
+        return float(loss), g
+
+    return objective
+
+
 def fit_map(train_x: Sequence[Tensor], train_y: Sequence[Tensor], model_config: dict,
-            fixed_means: Optional[Sequence[float]] = None, max_iter: int = 1000) -> Dict[str, object]:
+            fixed_means: Optional[Sequence[float]] = None, max_iter: int = 1000, device=None) -> Dict[str, object]:
     """Maximise the SumMarginalLogLikelihood of a ModelListGP built from ``model_config`` (the reference's
     ``model`` section: ``outputs[i]`` priors and ``fix_zero_noise``, ``fit_hyperparams``) on output i's data
     (train_x[i] in [0, 1]^d, train_y[i]); ``fixed_means``: the ``always`` path's constants after its first fit.
     Returns ``length_scales``, ``output_scales``, ``means``, ``noises`` (per output, bo_smoke's ``hyper``
-    layout), the final objective ``mll`` and the optimiser's ``success`` / ``iterations``."""
+    layout), the final objective ``mll`` and the optimiser's ``success`` / ``iterations``.
+
+    ``device`` (a ROCm device; default None: the host objective below, bit for bit as before): every objective
+    evaluation is one ``dkg_mll_value_grad`` call for all outputs on that device (data and workspace uploaded
+    once per fit), the priors and parameter transforms added on the host.  Same bounds, start, ``max_iter``,
+    jitter retries and return value.  The device takes the scaled distances from differences where ``matern``
+    expands |a|^2 + |b|^2 - 2 a.b."""
     from scipy.optimize import minimize
 
     min_noise_se = 1e-4 if model_config.get("fit_hyperparams", "once") == "never" else MIN_NOISE_SE
@@ -170,6 +337,8 @@ def fit_map(train_x: Sequence[Tensor], train_y: Sequence[Tensor], model_config: 
         (g,) = torch.autograd.grad(loss, raw)
         return float(loss.detach()), g.numpy().astype(np.float64)
 
+    if device is not None:
+        objective = _device_objective(outs, device)
     res = minimize(objective, x0, jac=True, method="L-BFGS-B", bounds=bounds, options={"maxiter": max_iter})
     raw = torch.tensor(res.x, dtype=torch.double)
     hyper: Dict[str, list] = {"length_scales": [], "output_scales": [], "means": [], "noises": []}

@@ -163,6 +163,34 @@ int dkg_append_observation(const dkg_output* o, int d, const double* L, const do
                            double* Linv_new, double* alpha_new, double* root_frag_new, double* disc_frag_new,
                            double* disc_mean_new, void* work, size_t work_bytes, void* stream);
 
+/* Bytes of device scratch dkg_mll_value_grad needs for m outputs of n[i] training points; 0 for a NULL n,
+ * m outside 1..DKG_MAX_OUTPUTS or an n[i] outside 1..1024. */
+size_t dkg_mll_workspace(const int* n, int m);
+
+/* The marginal log-likelihood of m outputs and its gradient in the hyperparameters, on the device: the objective
+ * of the MAP fit (the reference's fit_gpytorch_mll on ExactMarginalLogLikelihood, factory.py:24-151,
+ * bo_loop.py:63-79, 589-619) without priors, parameter transforms or the division by n, which stay with the
+ * caller.  Per output o (reads n, kernel, outputscale s, noise, mean_constant c, inv_lengthscale, train_x and
+ * train_y[o], device [n], model space), with K = s kappa(X, X) + (noise + jitter) I, L = chol(K), M = L^{-1},
+ * r = y - c, alpha = M^T M r, G = M^T M, W = alpha alpha^T - G and t_ik = (x_i - x_k) / l:
+ *   value[o] = log N(y | c 1, K) = -1/2 r.alpha - sum_i log L_ii - (n / 2) log 2 pi
+ *   grad[o]  = [d/dc, d/dl_1 .. d/dl_d, d/ds, d/dnoise]  (host [m][d + 3]; lengthscales l, not their inverses;
+ *              constrained space)
+ *     d/dc = sum_i alpha_i,  d/dnoise = 1/2 tr W,  d/ds = 1/2 sum_ik W_ik kappa_ik,
+ *     d/dl_j = -1/2 sum_ik W_ik s h(|t_ik|^2) t_ik,j^2 / l_j,  h = kappa'(r) / r (0 for Matern-1/2 at
+ *     r^2 <= 1e-30: the diagonal and duplicated training points, as the reference's distance clamp gives)
+ * The factorisation is dkg_prepare_outputs' own (all outputs in every launch; absolute jitter 1e-8 * 10^i,
+ * i < max_tries, for the outputs that fail; jitter_used: host [m], nullable); DKG_ERR_NOT_PD if every attempt
+ * failed.  The contraction runs over 32 x 32 tiles of the pair space with v_mfma_f64_16x16x4_f64; K^{-1} is
+ * never written to memory.  work: device scratch of dkg_mll_workspace() bytes, the only memory written besides
+ * the host results.  Synchronises `stream` (the results go to host memory).  Deterministic: every sum runs in a
+ * fixed order, no atomics.  DKG_ERR_UNSUPPORTED for n > 1024, m > DKG_MAX_OUTPUTS or d > DKG_MAX_DIM,
+ * DKG_ERR_ARG for NULL pointers or bad sizes, DKG_ERR_WORKSPACE for a short workspace; the arguments are
+ * checked before any HIP call. */
+int dkg_mll_value_grad(const dkg_output* outs, int m, int d, const double* const* train_y, int max_tries,
+                       void* work, size_t work_bytes, double* value, double* grad, double* jitter_used,
+                       void* stream);
+
 /* Bytes of scratch dkg_forward needs for (m outputs, N points, B candidates, S weights). */
 size_t dkg_forward_workspace(const dkg_output* outs, int m, int N, int B, int S);
 
