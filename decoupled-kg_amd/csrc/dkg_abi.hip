@@ -71,9 +71,12 @@ static int max_np_of(const dkg_output* outs, int m) {
   return np;
 }
 
-WsLayout layout(const dkg_output* outs, int m, int N, int B, int S, int d = 0, int flags = 0) {
+// T: the plan's targets (dkg_plan_init_targets).  The per-candidate result buffers hold one row per item
+// (tau, b) at tau * Bp + b: `items` rows where a single-target plan has max(B, 1), T * Bp where it has Bp.
+WsLayout layout(const dkg_output* outs, int m, int N, int B, int S, int d = 0, int flags = 0, int T = 1) {
   WsLayout L{};
   const size_t Bp = pad16(std::max(B, 1));
+  const size_t items = (size_t)(T - 1) * Bp + std::max(B, 1);
   // fused hand-off counters, one per 128-byte line: cnt1 [m][Bp / 16], cnt2 [ceil(B / 32)], done; then the err word
   L.sync_bytes = ((((size_t)m * (Bp / 16) + (Bp + 31) / 32 + 1) * HANDOFF_STRIDE * sizeof(unsigned long long) +
                    sizeof(int)) + 15) & ~(size_t)15;
@@ -133,15 +136,15 @@ WsLayout layout(const dkg_output* outs, int m, int N, int B, int S, int d = 0, i
   // split > 1: every pair's KG (and, value+gradient, its dKG/dx) for the last workgroup's ordered sums
   const size_t pcols = (size_t)std::max(S, 1) + pair_groups(std::max(S, 1));  // pair values + group terms
   L.wg_part = off;
-  off = align256(off + (split > 1 ? (size_t)std::max(B, 1) * pcols * sizeof(double) : 0));
+  off = align256(off + (split > 1 ? items * pcols * sizeof(double) : 0));
   L.wg_gpart = off;
-  off = align256(off + ((flags & DKG_PLAN_GRAD) && split > 1 ? (size_t)std::max(B, 1) * pcols * d * sizeof(double) : 0));
+  off = align256(off + ((flags & DKG_PLAN_GRAD) && split > 1 ? items * pcols * d * sizeof(double) : 0));
   L.tickets = off;
-  off = align256(off + Bp * (pair_groups(std::max(S, 1)) + 1) * sizeof(int));
+  off = align256(off + (size_t)T * Bp * (pair_groups(std::max(S, 1)) + 1) * sizeof(int));
   L.dup = off;
   off = align256(off + Bp * sizeof(int));
   L.hull_pairs = off;
-  off = align256(off + (size_t)std::max(B, 1) * std::max(S, 1) * sizeof(int));
+  off = align256(off + items * std::max(S, 1) * sizeof(int));
   if (N + 1 <= 64 * 33) {  // the staged forward's intercept cache (Plan::icpt)
     L.icpt = off;
     off = align256(off + (size_t)std::max(S, 1) * 64 * env_slots(N + 1) * sizeof(double));
@@ -171,12 +174,34 @@ int check_outputs(const dkg_output* outs, int m, int d) {
   return DKG_OK;
 }
 
+// The targets of a plan (dkg_plan_init_targets): 1 <= T <= m + 1 distinct entries in [-1, m).
+int check_targets(const int* targets, int T, int m) {
+  if (!targets) return fail(DKG_ERR_ARG, "targets is NULL");
+  if (T < 1 || T > m + 1 || T > DKG_MAX_OUTPUTS + 1)
+    return fail(DKG_ERR_ARG, "T=%d targets (1..%d for %d outputs)", T, m + 1, m);
+  for (int t = 0; t < T; ++t) {
+    if (targets[t] < -1 || targets[t] >= m)
+      return fail(DKG_ERR_ARG, "targets[%d]=%d out of range for %d outputs", t, targets[t], m);
+    for (int u = 0; u < t; ++u)
+      if (targets[u] == targets[t]) return fail(DKG_ERR_ARG, "targets[%d]=%d repeats targets[%d]", t, targets[t], u);
+  }
+  return DKG_OK;
+}
+
+// targets == nullptr: the single-target plan of `target`.
 int build_plan(const dkg_output* outs, int m, int d, const double* disc, int N, const double* weights, int S,
-               int target, int max_B, void* workspace, size_t workspace_bytes, Plan* P, int flags = 0) {
+               int target, int max_B, void* workspace, size_t workspace_bytes, Plan* P, int flags = 0,
+               const int* targets = nullptr, int T = 1) {
   int st = check_outputs(outs, m, d);
   if (st) return st;
   if (max_B < 0 || N < 0) return fail(DKG_ERR_ARG, "negative size B=%d N=%d", max_B, N);
   if (S < 1) return fail(DKG_ERR_ARG, "S=%d scalarisations", S);
+  if (targets) {
+    if ((st = check_targets(targets, T, m))) return st;
+    target = targets[0];
+    if (T > 1 && (flags & DKG_PLAN_FUSED))
+      return fail(DKG_ERR_UNSUPPORTED, "DKG_PLAN_FUSED runs one target per plan; got T=%d targets", T);
+  }
   if (target < -1 || target >= m) return fail(DKG_ERR_ARG, "target_output_ix=%d out of range for %d outputs", target, m);
   if (N > (1 << 22)) return fail(DKG_ERR_UNSUPPORTED, "N=%d discretisation points (supported <= %d)", N, 1 << 22);
   int sw, split;
@@ -201,7 +226,7 @@ int build_plan(const dkg_output* outs, int m, int d, const double* disc, int N, 
   if (want_grad && envelope_grad_lds_bytes(m, N, sw, S, d, max_np, true) > 160 * 1024)
     return fail(DKG_ERR_UNSUPPORTED, "gradient: m=%d outputs, n=%d, d=%d exceed the envelope stage's LDS", m, max_np,
                 d);
-  const WsLayout L = layout(outs, m, N, max_B, S, d, flags);
+  const WsLayout L = layout(outs, m, N, max_B, S, d, flags, T);
   if (workspace_bytes < L.total)
     return fail(DKG_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, L.total);
   char* ws = static_cast<char*>(workspace);
@@ -211,6 +236,11 @@ int build_plan(const dkg_output* outs, int m, int d, const double* disc, int N, 
   P->N = N;
   P->S = S;
   P->target = target;
+  P->ntgt = T;
+  for (int t = 0; t < T; ++t) {
+    P->tlist[t] = targets ? targets[t] : target;
+    P->tpack |= (unsigned long long)(P->tlist[t] + 1) << (4 * t);
+  }
   P->max_B = max_B;
   P->max_np = 16;
   P->sw = sw;
@@ -741,6 +771,9 @@ int dkg_plan_time_stage_batches(const void* host_plan, const void* dev_plan, con
   if (B < 1 || nbatch < 1) return fail(DKG_ERR_ARG, "B=%d nbatch=%d", B, nbatch);
   if (!host_plan) return fail(DKG_ERR_ARG, "NULL plan pointer");
   // (as dkg_plan_forward_batches: the product in 64 bits, so a wrapped int cannot pass the capacity check)
+  if (static_cast<const Plan*>(host_plan)->ntgt > 1)
+    return fail(DKG_ERR_UNSUPPORTED, "dkg_plan_time_stage_batches runs one target per plan; the plan has %d",
+                static_cast<const Plan*>(host_plan)->ntgt);
   if ((long long)B * nbatch > static_cast<const Plan*>(host_plan)->max_B)
     return fail(DKG_ERR_ARG, "%d batches of B=%d candidates > plan capacity %d", nbatch, B,
                 static_cast<const Plan*>(host_plan)->max_B);
@@ -764,6 +797,24 @@ int dkg_plan_init(const dkg_output* outs, int m, int d, const double* disc, int 
                    "hipMemcpyAsync");
 }
 
+size_t dkg_plan_workspace_targets(const dkg_output* outs, int m, int d, int N, int max_B, int S, int T, int flags) {
+  if (!outs || m < 1 || m > DKG_MAX_OUTPUTS || T < 1 || T > m + 1) return 0;
+  return layout(outs, m, N, max_B, S, d, flags, T).total;
+}
+
+int dkg_plan_init_targets(const dkg_output* outs, int m, int d, const double* disc, int N, const double* weights,
+                          int S, const int* targets, int T, int max_B, int flags, void* workspace,
+                          size_t workspace_bytes, void* host_plan, void* dev_plan, void* stream) {
+  if (!host_plan || !dev_plan) return fail(DKG_ERR_ARG, "NULL plan pointer");
+  if (!targets) return fail(DKG_ERR_ARG, "targets is NULL");
+  Plan* h = static_cast<Plan*>(host_plan);
+  int st = build_plan(outs, m, d, disc, N, weights, S, -1, max_B, workspace, workspace_bytes, h, flags, targets, T);
+  if (st) return st;
+  if ((st = copy_disc_means(*h, (hipStream_t)stream))) return st;
+  return hip_check(hipMemcpyAsync(dev_plan, h, sizeof(Plan), hipMemcpyHostToDevice, (hipStream_t)stream),
+                   "hipMemcpyAsync");
+}
+
 int dkg_plan_forward(const void* host_plan, const void* dev_plan, const double* xnew, int B, double* kg,
                      double* kg_pairs, void* stream) {
   if (!host_plan || !dev_plan) return fail(DKG_ERR_ARG, "NULL plan pointer");
@@ -775,6 +826,8 @@ int dkg_plan_forward_batches(const void* host_plan, const void* dev_plan, const 
                              double* kg, void* stream) {
   if (!host_plan || !dev_plan) return fail(DKG_ERR_ARG, "NULL plan pointer");
   const Plan& h = *static_cast<const Plan*>(host_plan);
+  if (h.ntgt > 1)
+    return fail(DKG_ERR_UNSUPPORTED, "dkg_plan_forward_batches runs one target per plan; the plan has %d", h.ntgt);
   if (B < 0 || nbatch < 0) return fail(DKG_ERR_ARG, "negative size B=%d nbatch=%d", B, nbatch);
   if ((long long)B * nbatch == 0) return DKG_OK;
   if ((long long)B * nbatch > h.max_B)
@@ -820,6 +873,7 @@ int dkg_plan_forward_grad_hostx(const void* host_plan, const void* dev_plan, con
   XArg xa;
   xa.n = B * h.d;
   for (int i = 0; i < xa.n; ++i) xa.v[i] = x_host[i];
+  // (several targets: out_host holds [kg (T x B) | dkg_dx (T x B x d)])
   int st = hip_check(launch_forward_grad(h, static_cast<const Plan*>(dev_plan), x_dev, B, kg, dkg_dx,
                                          (hipStream_t)stream, &xa, out_host),
                      "forward_grad_hostx");
@@ -846,6 +900,10 @@ int dkg_plan_hull_sizes(const void* host_plan, int* out, int B, void* stream) {
   const Plan& h = *static_cast<const Plan*>(host_plan);
   if (B < 0 || B > h.max_B) return fail(DKG_ERR_ARG, "B=%d outside [0, %d]", B, h.max_B);
   if (B == 0) return DKG_OK;
+  if (h.ntgt > 1)  // [T][B][S] out of the workspace's items (tau * bpad + b)
+    return hip_check(hipMemcpy2DAsync(out, sizeof(int) * (size_t)B * h.S, h.hull_pairs,
+                                      sizeof(int) * (size_t)h.bpad * h.S, sizeof(int) * (size_t)B * h.S, h.ntgt,
+                                      hipMemcpyDeviceToDevice, (hipStream_t)stream), "hipMemcpy2DAsync(hull sizes)");
   return hip_check(hipMemcpyAsync(out, h.hull_pairs, sizeof(int) * (size_t)B * h.S, hipMemcpyDeviceToDevice,
                                   (hipStream_t)stream), "hipMemcpyAsync(hull sizes)");
 }
@@ -891,6 +949,10 @@ int dkg_plan_lines(const void* host_plan, const void* dev_plan, const double* xn
   if (B < 0 || B > h.max_B) return fail(DKG_ERR_ARG, "B=%d outside [0, %d]", B, h.max_B);
   if (B == 0) return DKG_OK;
   if (!xnew || !intercepts || !slopes) return fail(DKG_ERR_ARG, "NULL data pointer");
+  // several targets: the lines of tlist[0]; the cross stage clears ntgt rows of B accumulators in `intercepts`
+  if ((long long)h.S * (h.N + 1) < h.ntgt)
+    return fail(DKG_ERR_UNSUPPORTED, "dkg_plan_lines: S*(N+1)=%lld doubles per candidate < the plan's %d targets",
+                (long long)h.S * (h.N + 1), h.ntgt);
   // (an F32 plan exports the lines its fp32 contractions give: the error model's check, tools/f32_debug.py)
   const Plan* dev = static_cast<const Plan*>(dev_plan);
   hipStream_t s = (hipStream_t)stream;

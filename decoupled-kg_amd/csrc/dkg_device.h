@@ -1496,7 +1496,8 @@ __host__ __device__ constexpr int env_waves_per_eu(int maxl, int m, bool grad, b
 // The line data (mu_all, cov_all), the candidate posteriors (var_all, mux_all)
 // and the weights arrive as arguments, so the first DMA issues after a
 // single kernel-argument load instead of a pointer chase through the plan.
-template <int MAXL, int M, bool GRAD, bool STREAM, bool HO = false>
+// MT (envelope_targets_kernel): item (tau, b) of a plan of ntgt targets, its target in the arguments.
+template <int MAXL, int M, bool GRAD, bool STREAM, bool HO = false, bool MT = false>
 __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B, double* __restrict__ kg,
                                               double* __restrict__ pairs_out, int dst,
                                               const double* __restrict__ xnew, double* __restrict__ dkg,
@@ -1505,7 +1506,8 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
                                               const double* __restrict__ mux_all, const double* __restrict__ wts,
                                               const int* __restrict__ dupv, long long cov_stride, int bpad, int b,
                                               int g, int G, double* smem, unsigned long long* st,
-                                              const Handoff* ho = nullptr, double* __restrict__ hout = nullptr) {
+                                              const Handoff* ho = nullptr, double* __restrict__ hout = nullptr,
+                                              int tau = 0, int ntgt = 1, int target_mt = -1) {
   static_assert(!HO || (!GRAD && !STREAM), "the fused forward stages its lines (no gradient, no streaming)");
   // per output i: y_std, y_mean, noise, outputscale, noiseless variance at x_b, mean at x_b (model space),
   // and line 0's inputs: the mean and slope component it is built from (x_b's own, or, when x_b coincides
@@ -1520,8 +1522,13 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
   const int N = P->N;
   const int NL = N + 1;
   const int S = P->S;
-  const int target = P->target;
+  // MT: item (tau, b) of a plan of several targets (Plan::tlist): candidate b's records under target tlist[tau],
+  // which arrives with the kernel arguments; the results go to the item's own rows (ib: the caller's buffers,
+  // iw: the workspace's), so the combines below never mix two targets.  One target: ib = iw = b.
+  const int target = MT ? target_mt : P->target;
   const bool full = target < 0;
+  const size_t ib = MT ? (size_t)tau * B + b : (size_t)b, iw = MT ? (size_t)tau * bpad + b : (size_t)b;
+  const size_t nitems = MT ? (size_t)ntgt * B : (size_t)B;  // rows of kg in the pinned host copy [kg | dkg]
   static_assert(STREAM || MAXL == 2 || MAXL == 8 || MAXL == 17 || MAXL == 33, "slot bucket");
   KST_BEGIN(st);
 
@@ -2402,7 +2409,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
       sf = (scnt <= LIST_CAP_STREAM) ? list_extremes(scnt, lane, sb, sa) : env_extremes_stream<MAXL>(nch, NL, lane,
                                                                                                      build_chunk);
 #ifdef DKG_STG_STAMPS
-      if (lane == 0) P->hull_pairs[(size_t)b * S + j] = scnt;  // diagnostics build: the list length per pair
+      if (lane == 0) P->hull_pairs[iw * S + j] = scnt;  // diagnostics build: the list length per pair
 #endif
 #endif
       if (sf.status == 1) {
@@ -2516,11 +2523,11 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
       }
     }
     if (pairs_out != nullptr && lane == 0) {
-      pairs_out[(size_t)b * S + j] = kgj;
+      pairs_out[ib * S + j] = kgj;
 #ifdef DKG_STG_STAMPS
-      if constexpr (!GRAD && !STG) P->hull_pairs[(size_t)b * S + j] = hn;  // STG: the list length, above
+      if constexpr (!GRAD && !STG) P->hull_pairs[iw * S + j] = hn;  // STG: the list length, above
 #else
-      if constexpr (!GRAD) P->hull_pairs[(size_t)b * S + j] = hn;
+      if constexpr (!GRAD) P->hull_pairs[iw * S + j] = hn;
 #endif
     }
     if (lane == 0) skg[j - j0] = kgj;
@@ -2551,8 +2558,8 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
     const int grp = j0 >> 3;
     const int gpairs = min(8, S - 8 * grp);      // pairs in this workgroup's group
     const int gwgs = (gpairs + SW - 1) / SW;     // workgroups sharing it (1 unless the launch is narrow)
-    const size_t prow = (size_t)b * (S + ng);    // wg_part row of candidate b: S pair values, ng group terms
-    int* tk = P->tickets + (size_t)b * (ng + 1); // [ng] group tickets, [ng] the candidate's
+    const size_t prow = iw * (S + ng);           // wg_part row of the item: S pair values, ng group terms
+    int* tk = P->tickets + iw * (ng + 1);        // [ng] group tickets, [ng] the item's
     __shared__ int s_last;
     const int dg = GRAD ? d : 0;
     // ---- level 1: G_g (thread 0) and, GRAD, its gradient (threads 1 .. d, one coordinate each)
@@ -2587,9 +2594,10 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
     }
     const bool holds = (gwgs == 1 || s_last) && (threadIdx.x == 0 || (GRAD && gi >= 0 && gi < dg));
     const double term = gsum / (double)S;
-    // where this thread's result goes: kg[b] (thread 0) or dkg[b][gi]; the host copy at the same offsets
-    double* dst_dev = threadIdx.x == 0 ? &kg[b] : (GRAD ? &dkg[(size_t)b * d + max(gi, 0)] : &kg[b]);
-    const size_t hoff = threadIdx.x == 0 ? (size_t)b : (size_t)B + (size_t)b * d + max(gi, 0);
+    // where this thread's result goes: kg[ib] (thread 0) or dkg[ib][gi]; the host copy [kg | dkg] at the same
+    // offsets
+    double* dst_dev = threadIdx.x == 0 ? &kg[ib] : (GRAD ? &dkg[ib * d + max(gi, 0)] : &kg[ib]);
+    const size_t hoff = threadIdx.x == 0 ? ib : nitems + ib * d + max(gi, 0);
     // ---- level 2
     const bool fold = ng > 2 || (hout != nullptr && ng > 1);
     if (ng == 1) {
@@ -2658,6 +2666,33 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(env_waves_p
   if (!xcd_group(blockIdx.x, B, split, b, g)) return;
   envelope_body<MAXL, M, GRAD, STREAM>(P, B, kg, pairs_out, dst, xnew, dkg, mu_all, cov_all, var_all, mux_all, wts,
                                        dupv, cov_stride, bpad, b, g, split, smem, kst_slot(dst, P, 2), nullptr, hout);
+}
+
+// The envelope stage of a plan of ntgt > 1 targets: ntgt * split workgroups per candidate, side by side on one
+// XCD (member = tau * split + g), so the candidate's records come from HBM once for all of its items.  The same
+// body, so an item's bits are the single-target kernel's.
+template <int MAXL, int M, bool GRAD, bool STREAM>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(env_waves_per_eu(MAXL, M, GRAD, STREAM)))) void envelope_targets_kernel(const Plan* __restrict__ P, int B, double* __restrict__ kg,
+                                                       double* __restrict__ pairs_out, int dst,
+                                                       const double* __restrict__ xnew, double* __restrict__ dkg,
+                                                       const double* __restrict__ mu_all,
+                                                       const double* __restrict__ cov_all,
+                                                       const double* __restrict__ var_all,
+                                                       const double* __restrict__ mux_all,
+                                                       const double* __restrict__ wts,
+                                                       const int* __restrict__ dupv, long long cov_stride,
+                                                       int bpad, double* __restrict__ hout, int split,
+                                                       int ntgt, unsigned long long tpack) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  if (DKG_ABLATIONS && (__builtin_amdgcn_readfirstlane(P->debug_env) & 2)) return;  // ablation: empty envelope stage
+  int b, g;
+  if (!xcd_group(blockIdx.x, B, split * ntgt, b, g)) return;
+  const int tau = g / split;
+  g -= tau * split;
+  envelope_body<MAXL, M, GRAD, STREAM, false, true>(P, B, kg, pairs_out, dst, xnew, dkg, mu_all, cov_all, var_all,
+                                                    mux_all, wts, dupv, cov_stride, bpad, b, g, split, smem,
+                                                    kst_slot(dst, P, 2), nullptr, hout, tau, ntgt,
+                                                    target_of(tpack, tau));
 }
 
 // The lines of every (candidate, scalarisation) pair of the plan's last
@@ -2732,8 +2767,15 @@ struct EnvLaunch {
 
 template <int MAXL, int M, bool GRAD, bool STREAM>
 hipError_t launch_env_t(const EnvLaunch& a) {
-  raise_lds_limit((const void*)envelope_kernel<MAXL, M, GRAD, STREAM>, a.lds);
   const Plan& h = *a.host;
+  if (h.ntgt > 1) {
+    raise_lds_limit((const void*)envelope_targets_kernel<MAXL, M, GRAD, STREAM>, a.lds);
+    hipLaunchKernelGGL((envelope_targets_kernel<MAXL, M, GRAD, STREAM>), a.grid, a.block, a.lds, a.s, a.dev, a.B, a.kg,
+                       a.pairs, a.dst, a.xnew, a.dkg, h.mu_all, h.cov_all, h.var_all, h.mux_all, h.weights, h.dup,
+                       (long long)h.cov_stride, h.bpad, a.hout, h.split, h.ntgt, h.tpack);
+    return hipGetLastError();
+  }
+  raise_lds_limit((const void*)envelope_kernel<MAXL, M, GRAD, STREAM>, a.lds);
   hipLaunchKernelGGL((envelope_kernel<MAXL, M, GRAD, STREAM>), a.grid, a.block, a.lds, a.s, a.dev, a.B, a.kg, a.pairs,
                      a.dst, a.xnew, a.dkg, h.mu_all, h.cov_all, h.var_all, h.mux_all, h.weights, h.dup,
                      (long long)h.cov_stride, h.bpad, a.hout, h.split);

@@ -110,7 +110,23 @@ struct Plan {
   int* itopk;                       // [S][2]: the first k >= 1 attaining it, and how many lines do
   float* kx32[DKG_MAX_OUTPUTS];     // F32 with the K(x, X) fill: kx's entries quad-packed in fp32 (frag32_index),
                                     // the B operand of cross_big32_kernel (kx itself still feeds the fp64 means)
+  // Several targets on one plan (dkg_plan_init_targets): the cross and covariance stages do not depend on the
+  // target, so one call runs them once and the envelope once per item (tau, b), target tlist[tau]
+  // (envelope_targets_kernel; a plan of one target launches envelope_kernel, which knows nothing of items).  The
+  // per-candidate result buffers (kg accumulators, wg_part, wg_gpart, tickets, hull_pairs) are carved per item,
+  // workspace item tau * bpad + b; the caller's kg / dkg_dx / kg_pairs rows are item tau * B + b.
+  // ntgt = 1, tlist[0] = target: the single-target plan.
+  int32_t ntgt;
+  int32_t tlist[DKG_MAX_OUTPUTS + 1];
+  // tlist for the envelope kernel's arguments: 4 bits per target, tlist[tau] + 1 at bits 4 tau (target_of), so
+  // a workgroup has its target with the argument load instead of a dependent load through the plan
+  unsigned long long tpack;
 };
+
+__host__ __device__ inline int target_of(unsigned long long tpack, int tau) {
+  return (int)((tpack >> (4 * tau)) & 15) - 1;
+}
+static_assert(DKG_MAX_OUTPUTS + 1 <= 15 && 4 * (DKG_MAX_OUTPUTS + 1) <= 64, "Plan::tpack holds every target in 4 bits");
 
 // By-value arguments of the state-preparation use of the cross stage.
 struct CrossArgs {

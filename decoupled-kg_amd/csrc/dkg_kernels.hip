@@ -192,6 +192,14 @@ __device__ inline void clear_tile_accumulators(const Plan* __restrict__ P, doubl
     P->dup[i] = DUP_NONE;
   }
   for (int i = b0 * ng1 + (int)threadIdx.x; i < b1 * ng1; i += blockDim.x) P->tickets[i] = 0;
+  // a plan of several targets: the same rows of every further item (caller's kg row tau * B + b, tickets of
+  // workspace item tau * bpad + b)
+  const int nt = P->ntgt;
+  for (int t = 1; t < nt; ++t) {
+    for (int i = b0 + (int)threadIdx.x; i < b1; i += blockDim.x) kg[(size_t)t * B + i] = 0.0;
+    int* tk = P->tickets + (size_t)t * P->bpad * ng1;
+    for (int i = b0 * ng1 + (int)threadIdx.x; i < b1 * ng1; i += blockDim.x) tk[i] = 0;
+  }
 }
 
 // Forward: grid (B tiles, pairs, outputs); the first workgroup of every row tile also clears that
@@ -363,7 +371,7 @@ __global__ __launch_bounds__(CR_WAVES * WAVE) void cross_fwd_grad_kernel(const P
   }
   const int oi = (z - m) / d, gdim = (z - m) % d;
   if (blockIdx.x == 0 && blockIdx.y == 0 && z == m)
-    for (int i = threadIdx.x; i < B * d; i += blockDim.x) dkg[i] = 0.0;
+    for (int i = threadIdx.x; i < P->ntgt * B * d; i += blockDim.x) dkg[i] = 0.0;  // [ntgt][B][d]
   const dkg_output& o = P->o[oi];
   const size_t mat = (size_t)P->bpad * pad16(o.n);
   cross_root_impl<DM, true>(o, d, xnew, B, P->jq[oi] + gdim * mat, P->gmu[oi] + (size_t)gdim * P->bpad, blockIdx.x,
@@ -868,7 +876,8 @@ hipError_t launch_stage(const Plan& h, const Plan* dev, const double* xnew, int 
       default: return launch_cross_cov_t<16>(h, dev, xnew, B, kg, s, stage, gb);
     }
   }
-  EnvLaunch a{&h, dev, B, kg, pairs, dim3(xcd_group_size(B, h.split)), dim3(h.sw * WAVE),
+  // (several targets: ntgt items per candidate, the workgroups of a candidate's items side by side)
+  EnvLaunch a{&h, dev, B, kg, pairs, dim3(xcd_group_size(B, h.split * h.ntgt)), dim3(h.sw * WAVE),
               envelope_lds_bytes(h.m, h.N, h.sw, h.S, h.stream != 0, false, !DKG_ICP), s, h.debug_stamp, nullptr,
               nullptr};
   return launch_env<false>(h, a);
@@ -899,7 +908,7 @@ hipError_t launch_forward_grad(const Plan& h, const Plan* dev, const double* xne
   }
   if (e != hipSuccess) return e;
   if ((e = launch_stage(h, dev, xnew, B, kg, nullptr, s, 1)) != hipSuccess) return e;  // cov rows, variances
-  EnvLaunch a{&h, dev, B, kg, nullptr, dim3(xcd_group_size(B, h.split)), dim3(h.sw * WAVE),
+  EnvLaunch a{&h, dev, B, kg, nullptr, dim3(xcd_group_size(B, h.split * h.ntgt)), dim3(h.sw * WAVE),
               envelope_grad_lds_bytes(h.m, h.N, h.sw, h.S, h.d, h.max_np, h.stream != 0), s, h.debug_stamp, xnew, dkg,
               hout};
   return launch_env<true>(h, a);

@@ -13,6 +13,7 @@ from .discretekg import (
     calculate_discrete_kg_conditioning_on_single_output,
     clear_state_cache,
     kg_from_lines,
+    normalise_targets,
     t_batch_mode_transform,
 )
 from .errors import BotorchTensorDimensionError, DkgNativeError, UnsupportedError
@@ -29,6 +30,7 @@ __all__ = [
     "calculate_discrete_kg_conditioning_on_single_output",
     "clear_state_cache",
     "kg_from_lines",
+    "normalise_targets",
     "t_batch_mode_transform",
     "BotorchTensorDimensionError",
     "DkgNativeError",

@@ -85,6 +85,10 @@ SIGNATURES = {
     "dkg_plan_workspace": (c_size_t, [POINTER(DkgOutput), c_int, c_int, c_int, c_int, c_int, c_int]),
     "dkg_plan_init": (c_int, [POINTER(DkgOutput), c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int,
                               c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),
+    "dkg_plan_workspace_targets": (c_size_t, [POINTER(DkgOutput), c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "dkg_plan_init_targets": (c_int, [POINTER(DkgOutput), c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                      POINTER(c_int), c_int, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                      c_void_p]),
     "dkg_plan_forward_grad": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "dkg_plan_forward_grad_hostx": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                             c_void_p, c_void_p]),

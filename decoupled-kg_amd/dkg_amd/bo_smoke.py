@@ -135,7 +135,7 @@ def run_mobo(problem: GPProblem, hyper: Dict[str, Sequence[float]], separate: bo
              spec: Optional[DiscreteKgOptimisationSpec] = None, seed: int = 0,
              catalog: Optional[DataCatalog] = None, run_key: Optional[str] = None,
              fit_hyperparams: str = "never", incremental: bool = False,
-             fit_on_device: bool = False) -> Dict[str, List]:
+             fit_on_device: bool = False, joint_objectives: bool = False) -> Dict[str, List]:
     """``bo_loop.run_mobo`` with the discrete-KG strategy for ``n_iter`` BO steps; returns the
     query history (x, objective index or None for full evaluation, observed values, acquisition).
     With ``catalog`` it also writes the reference's checkpoints and query-history table under
@@ -151,21 +151,24 @@ def run_mobo(problem: GPProblem, hyper: Dict[str, Sequence[float]], separate: bo
     to n = 10 -- a device evaluation costs its launches and two synchronisations whatever n is, 0.24 ms there,
     against the host's 0.87 ms; 2.5 against 62 ms at n = 1000.  Opt-in all the same: the two routes take the scaled
     distances differently, so their fits agree to the optimiser's tolerance, not bit for bit, and
-    the default keeps the host route's results."""
+    the default keeps the host route's results.  ``joint_objectives`` (``separate`` only; off by default, not the
+    reference's search): the query step passes ``joint=True`` to ``optimize_for_single_objective`` -- one
+    ``optimize_acqf`` run on max_t max(KG_t, 0) / cost_t instead of one per objective."""
     if fit_hyperparams not in ("never", "once", "always"):
         raise ValueError(f"Unexpected value for fit_hyperparams. Got {fit_hyperparams!r}")
     on = incremental and fit_hyperparams != "always"
     prev = set_incremental_state(True) if on else None
     try:
         return _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations, spec, seed, catalog,
-                         run_key, fit_hyperparams, _fit_device(problem, fit_on_device and fit_hyperparams == "always"))
+                         run_key, fit_hyperparams, _fit_device(problem, fit_on_device and fit_hyperparams == "always"),
+                         joint_objectives)
     finally:
         if on:
             set_incremental_state(prev)
 
 
 def _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations, spec, seed, catalog, run_key,
-              fit_hyperparams, fit_device=None) -> Dict[str, List]:
+              fit_hyperparams, fit_device=None, joint_objectives=False) -> Dict[str, List]:
     m, d = problem.num_objectives, problem.gp.input_dim
     # the pipeline's --seed (main.py:235, utils.set_random_seed): every later draw comes from the global RNG, as
     # in the reference -- the initial Sobol points (generate_initial_data, bo_loop.py:48-49: no seed), each
@@ -219,7 +222,8 @@ def _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations,
         W = sample_simplex(m, n_scalarisations, qmc=True, seed=seed + 1 + it, dtype=torch.double)
         w_row = W[0].numpy().copy() if W.shape[0] == 1 else None
         if separate:
-            x, i, acq = spec.optimize_for_single_objective(model, costs, d, scalarisation_weights=W)
+            x, i, acq = spec.optimize_for_single_objective(model, costs, d, scalarisation_weights=W,
+                                                           **({"joint": True} if joint_objectives else {}))
             x = x.reshape(1, d).cpu()
             y = problem(x)[0]
             train_x[i] = torch.cat([train_x[i], x])
@@ -256,13 +260,14 @@ def _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations,
 
 def run_smoke(problem: GPProblem, hyper: Dict[str, Sequence[float]], seed: int = 0,
               catalog: Optional[DataCatalog] = None, fit_hyperparams: str = "never",
-              incremental: bool = False, fit_on_device: bool = False) -> Dict[str, Dict]:
+              incremental: bool = False, fit_on_device: bool = False,
+              joint_objectives: bool = False) -> Dict[str, Dict]:
     """``run_pipeline`` under ``SMOKE_TEST`` (``main.py:171-216``): the separate-evaluation run and
     the full-evaluation run, two BO steps each; with ``catalog`` both write the reference's files.
     ``fit_hyperparams = "once"`` fits the hyperparameters first (``main.py:181-182``, saved to the catalog's
     ``hyperparameters.pt`` as the fitted surrogate's state dict) and both runs use them; ``"always"`` refits
     inside the runs.  ``incremental``, ``fit_on_device``: as ``run_mobo``'s (``fit_on_device`` also moves the
-    ``once`` fit's objective to the device)."""
+    ``once`` fit's objective to the device); ``joint_objectives``: as ``run_mobo``'s, for the separate run."""
     if fit_hyperparams == "once":
         torch.manual_seed(seed)
         cfg = reference_model_config(problem.num_objectives, problem.bounds, "once")
@@ -274,7 +279,7 @@ def run_smoke(problem: GPProblem, hyper: Dict[str, Sequence[float]], seed: int =
                 to_state_dict(surrogate([x] * problem.num_objectives, [y] * problem.num_objectives, hyper), cfg))
     return {"separate": run_mobo(problem, hyper, separate=True, seed=seed, catalog=catalog,
                                  fit_hyperparams=fit_hyperparams, incremental=incremental,
-                                 fit_on_device=fit_on_device),
+                                 fit_on_device=fit_on_device, joint_objectives=joint_objectives),
             "full": run_mobo(problem, hyper, separate=False, seed=seed, catalog=catalog,
                              fit_hyperparams=fit_hyperparams, incremental=incremental,
                              fit_on_device=fit_on_device)}

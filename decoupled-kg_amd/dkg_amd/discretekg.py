@@ -257,6 +257,77 @@ class _HostForwardFn(torch.autograd.Function):
         return (out if ctx.xdtype == torch.double else out.to(ctx.xdtype)), None
 
 
+def normalise_targets(targets, num_outputs: int) -> tuple:
+    """The targets of ``forward_targets`` as ``target_output_ix`` reads each of them: ``None`` is all outputs
+    observed, a negative index counts from the end, one out of range raises ``IndexError`` (the reference
+    indexes the outputs with it, discretekg.py:301-321).  ``targets=None``: ``[None, 0, ..., m - 1]``.
+    Entries that name the same target after that raise ``ValueError``."""
+    m = int(num_outputs)
+    if targets is None:
+        return (None,) + tuple(range(m))
+    out = []
+    for t in targets:
+        if t is None:
+            out.append(None)
+            continue
+        t = int(t)
+        if not -m <= t < m:
+            raise IndexError("list index out of range")
+        out.append(t % m)
+    if not out:
+        raise ValueError("targets is empty")
+    if len(set(out)) != len(out):
+        raise ValueError(f"targets name the same target more than once: {list(targets)} -> {out}")
+    return tuple(out)
+
+
+class _TargetsForwardFn(torch.autograd.Function):
+    """``_ForwardFn`` on a plan of T targets: KG [T, B]; backward of row tau is that target's dKG/dx scaled
+    by the incoming gradient, summed over the rows (every row depends on the same x_b)."""
+
+    @staticmethod
+    def forward(ctx, X, acq, key):
+        if ctx.needs_input_grad[0]:
+            kg, dkg = acq._targets_plan_for(key, X.shape[0], grad=True).forward_grad(X)
+            ctx.save_for_backward(dkg)
+            return kg
+        return acq._targets_plan_for(key, X.shape[0]).forward(X)
+
+    @staticmethod
+    def backward(ctx, grad):
+        (dkg,) = ctx.saved_tensors  # [T, B, d]
+        return (grad.to(dkg)[:, :, None] * dkg).sum(0), None, None
+
+
+class _TargetsHostForwardFn(torch.autograd.Function):
+    """``_HostForwardFn`` on a plan of T targets: host X [*batch, 1, d] -> KG [T, *batch], one device round
+    trip for all targets and a host-side backward."""
+
+    @staticmethod
+    def forward(ctx, X, acq, key):
+        d = X.shape[-1]
+        batch = X.shape[:-2]
+        xs = X
+        if xs.dtype is not torch.double or not xs.is_contiguous():
+            xs = xs.detach().to(torch.double).contiguous()
+        B = xs.numel() // d
+        T = len(key)
+        if ctx.needs_input_grad[0]:
+            kg, dkg = acq._targets_plan_for(key, B, grad=True).forward_grad_host(xs.reshape(B, d))
+            ctx.save_for_backward(dkg.reshape((T,) + X.shape))
+            ctx.xdtype = X.dtype
+            return kg.to(X.dtype).reshape((T,) + batch)
+        kg = acq._targets_plan_for(key, B).forward_host(xs.reshape(B, d))
+        return kg.to(X.dtype).reshape((T,) + batch)
+
+    @staticmethod
+    def backward(ctx, grad):
+        (dkg,) = ctx.saved_tensors  # [T, *batch, 1, d]
+        g = grad.to(dkg) if grad.dtype != dkg.dtype else grad
+        out = (g.reshape(g.shape + (1, 1)) * dkg).sum(0)
+        return (out if ctx.xdtype == torch.double else out.to(ctx.xdtype)), None, None
+
+
 class DiscreteKnowledgeGradient(_Base):
     """Discrete knowledge gradient (C-MOKG), linear scalarisations only."""
 
@@ -324,6 +395,8 @@ class DiscreteKnowledgeGradient(_Base):
         self._W = scalarisation_weights.detach().to(self._state.device, torch.double, copy=True).contiguous()
         self._plan = None
         self._plan_grad = None
+        # the plans of several targets (forward_targets), by (target tuple, with gradient buffers)
+        self._plans_targets = {}
 
     def _refresh(self):
         """Rebuild the device state if the model changed since it was read (see _fingerprint), and the plans
@@ -336,6 +409,7 @@ class DiscreteKnowledgeGradient(_Base):
                                        owner=self.model)
             self._plan = None
             self._plan_grad = None
+            self._plans_targets = {}
             self._fp = fp
         wfp = _weights_fingerprint(self.scalarisation_weights)
         if wfp != self._wfp:
@@ -346,6 +420,7 @@ class DiscreteKnowledgeGradient(_Base):
             self._W = w.detach().to(self._state.device, torch.double, copy=True).contiguous()
             self._plan = None
             self._plan_grad = None
+            self._plans_targets = {}
             self._wfp = wfp
 
     def invalidate(self) -> None:
@@ -415,6 +490,64 @@ class DiscreteKnowledgeGradient(_Base):
             plan = self._plan_for(B, grad=True)
         batch = X.shape[:-2] if X.dim() > 2 else X.shape[:-1]
         return plan.forward_grad_host_shaped(xs, B, batch, X.shape)
+
+    def _targets_plan_for(self, key: tuple, B: int, grad: bool = False):
+        """The plan of the targets ``key`` (``normalise_targets``), kept beside ``_plan`` / ``_plan_grad`` by
+        (key, grad) and grown as ``_plan_for`` grows them; ``_refresh`` drops these with the other two."""
+        cur = self._plans_targets.get((key, grad))
+        if cur is None or cur.max_B < B:
+            cap = 1
+            while cap < B:
+                cap *= 2
+            if grad and self.precision == "fp32":
+                raise UnsupportedError("precision='fp32' is forward only; use precision='fp64' for gradients")
+            cur = self._state.plan(self._W, None, max(cap, 16), grad=grad, f32=self.precision == "fp32",
+                                   targets=key)
+            self._plans_targets[(key, grad)] = cur
+        return cur
+
+    @t_batch_mode_transform(expected_q=1)
+    def forward_targets(self, X: Tensor, targets=None) -> Tensor:
+        """KG of every candidate under every target of ``targets`` in one pass: ``X[*batch, 1, d] ->
+        [T, *batch]``, row tau bit for bit the ``forward`` of an acquisition with ``target_output_ix =
+        targets[tau]``.  The cross and covariance stages, which do not depend on the target, run once per call
+        instead of once per target.  ``targets=None``: ``[None, 0, ..., m - 1]`` (``normalise_targets``).
+        Differentiable on both routes (host X, device X); this acquisition's own ``target_output_ix`` plays
+        no part."""
+        batch_shape, d = X.shape[:-2], X.shape[-1]
+        if d != self.x_discretisation.shape[-1]:
+            raise RuntimeError(
+                f"Expected X to have last dimension matching 'self.x_discretisation'. "
+                f"Got {X.shape[-1]=}, {self.x_discretisation.shape[-1]=}.")
+        self._refresh()
+        key = normalise_targets(targets, self._W.shape[-1])
+        if X.device.type == "cpu":
+            return _TargetsHostForwardFn.apply(X, self, key)
+        Xd = X.reshape(-1, d).to(self._state.device, torch.double)
+        kg = _TargetsForwardFn.apply(Xd, self, key)
+        return kg.to(device=X.device, dtype=X.dtype).reshape((len(key),) + tuple(batch_shape))
+
+    def value_and_grad_host_targets(self, X: Tensor, targets=None):
+        """``value_and_grad_host`` under every target of ``targets`` with one device round trip: host fp64
+        ``(kg [T, *batch], dkg [T, *X.shape])`` for host candidates X (``[*batch, 1, d]`` or ``[B, d]``),
+        row tau the bits of ``value_and_grad_host`` of an acquisition with ``target_output_ix = targets[tau]``."""
+        d = self.x_discretisation.shape[-1]
+        if X.shape[-1] != d:
+            raise RuntimeError(
+                f"Expected X to have last dimension matching 'self.x_discretisation'. "
+                f"Got {X.shape[-1]=}, {self.x_discretisation.shape[-1]=}.")
+        if X.dim() > 2 and X.shape[-2] != 1:
+            raise ValueError(f"Expected X to be `batch_shape x q=1 x d`, but got X with shape {tuple(X.shape)}.")
+        self._refresh()
+        key = normalise_targets(targets, self._W.shape[-1])
+        xs = X
+        if xs.dtype is not torch.double or not xs.is_cpu or not xs.is_contiguous():
+            xs = xs.detach().to("cpu", torch.double).contiguous()
+        B = xs.numel() // d
+        batch = X.shape[:-2] if X.dim() > 2 else X.shape[:-1]
+        kg, dkg = self._targets_plan_for(key, B, grad=True).forward_grad_host(xs.reshape(B, d))
+        T = len(key)
+        return kg.reshape((T,) + tuple(batch)), dkg.reshape((T,) + tuple(X.shape))
 
     def forward_pairs(self, X: Tensor) -> Tensor:
         """KG per (candidate, scalarisation): [B, S] (the per-``j`` values of ``:200-233``)."""

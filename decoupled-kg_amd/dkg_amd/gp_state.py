@@ -293,8 +293,8 @@ class DeviceGPState:
         return st
 
     def plan(self, W: torch.Tensor, target, max_B: int, grad: bool = False, force_walk: bool = False,
-             f32: bool = False, fused: bool = False, no_chain: bool = False) -> "ForwardPlan":
-        return ForwardPlan(self, W, target, max_B, grad, force_walk, f32, fused, no_chain)
+             f32: bool = False, fused: bool = False, no_chain: bool = False, targets=None) -> "ForwardPlan":
+        return ForwardPlan(self, W, target, max_B, grad, force_walk, f32, fused, no_chain, targets=targets)
 
     def forward(self, X: torch.Tensor, W: torch.Tensor, target, kg_pairs=None, timed: bool = False):
         """One-shot forward (builds a plan on the fly); see ForwardPlan for the fast path."""
@@ -309,10 +309,18 @@ class ForwardPlan:
     kernels, or with ``fused=True`` one launch whose stages hand off inside it
     (dkg_fused.h; same bits, not faster on MI355X: DESIGN.md 4.8).  With ``grad=True`` the
     workspace also holds the gradient buffers and ``forward_grad`` returns
-    dKG/dx alongside KG."""
+    dKG/dx alongside KG.
+
+    ``targets`` (a sequence of ``None`` / output indices, distinct; ``target`` is then ignored): a plan of
+    T targets (``dkg_plan_init_targets``).  Every call runs the cross and covariance stages once and the
+    envelope once per (target, candidate), and ``forward`` / ``forward_into`` / ``forward_grad`` /
+    ``forward_grad_host`` / ``forward_host`` / ``forward_stats`` return tensors with a leading T axis, row
+    tau bit for bit what a single-target plan of ``targets[tau]`` returns.  Not with ``fused`` or
+    ``forward_batches_into`` (``UnsupportedError``); ``lines`` exports the lines of ``targets[0]``."""
 
     def __init__(self, state: DeviceGPState, W: torch.Tensor, target, max_B: int, grad: bool = False,
-                 force_walk: bool = False, f32: bool = False, fused: bool = False, no_chain: bool = False):
+                 force_walk: bool = False, f32: bool = False, fused: bool = False, no_chain: bool = False,
+                 targets=None):
         lib = _lib.load()
         self.state = state
         self.device = state.device
@@ -322,6 +330,20 @@ class ForwardPlan:
         if self.W.dim() != 2 or self.W.shape[1] != state.m:
             raise ValueError(f"weights must be S x {state.m}")
         self.S = self.W.shape[0]
+        self.targets = None  # a plan of several targets: their C values (-1: all outputs), else None
+        if targets is not None:
+            tl = []
+            for t in targets:
+                if t is not None and not (0 <= int(t) < state.m):
+                    raise ValueError(f"targets must be None (all outputs) or in [0, {state.m}), got {t}")
+                tl.append(-1 if t is None else int(t))
+            if not tl:
+                raise ValueError("targets is empty")
+            if len(set(tl)) != len(tl):
+                raise ValueError(f"targets repeats an entry: {list(targets)}")
+            self.targets = tuple(tl)
+            target = None if tl[0] < 0 else tl[0]
+        self._nt = 1 if self.targets is None else len(self.targets)
         if target is not None and not (0 <= int(target) < state.m):
             # the C ABI's -1 means "all outputs observed": a negative index never reaches it
             raise ValueError(f"target must be None (all outputs) or in [0, {state.m}), got {target}")
@@ -332,21 +354,37 @@ class ForwardPlan:
         flags = ((_lib.DKG_PLAN_GRAD if self.grad else 0) | (_lib.DKG_PLAN_FORCE_WALK if force_walk else 0)
                  | (_lib.DKG_PLAN_F32 if self.f32 else 0) | (_lib.DKG_PLAN_FUSED if fused else 0)
                  | (_lib.DKG_PLAN_NO_CHAIN if no_chain else 0))
-        need = lib.dkg_plan_workspace(state.structs, state.m, state.d, state.N, self.max_B, self.S, flags)
-        self.ws = torch.zeros(max(need, 256), dtype=torch.uint8, device=self.device)
         nbytes = lib.dkg_plan_bytes()
         self.host = ctypes.create_string_buffer(nbytes)
-        self.dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        _lib.check(lib.dkg_plan_init(state.structs, state.m, state.d, _lib.ptr(state.D), state.N, _lib.ptr(self.W),
-                                     self.S, self.target, self.max_B, flags, _lib.ptr(self.ws), self.ws.numel(),
-                                     self.host, _lib.ptr(self.dev), current_stream_ptr(self.device)),
-                   "dkg_plan_init")
+        if self.targets is not None:
+            T = self._nt
+            tl = (ctypes.c_int * T)(*self.targets)
+            need = lib.dkg_plan_workspace_targets(state.structs, state.m, state.d, state.N, self.max_B, self.S, T,
+                                                  flags)
+            self.ws = torch.zeros(max(need, 256), dtype=torch.uint8, device=self.device)
+            self.dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _lib.check(lib.dkg_plan_init_targets(state.structs, state.m, state.d, _lib.ptr(state.D), state.N,
+                                                 _lib.ptr(self.W), self.S, tl, T, self.max_B, flags,
+                                                 _lib.ptr(self.ws), self.ws.numel(), self.host, _lib.ptr(self.dev),
+                                                 current_stream_ptr(self.device)), "dkg_plan_init_targets")
+        else:
+            need = lib.dkg_plan_workspace(state.structs, state.m, state.d, state.N, self.max_B, self.S, flags)
+            self.ws = torch.zeros(max(need, 256), dtype=torch.uint8, device=self.device)
+            self.dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            _lib.check(lib.dkg_plan_init(state.structs, state.m, state.d, _lib.ptr(state.D), state.N,
+                                         _lib.ptr(self.W), self.S, self.target, self.max_B, flags, _lib.ptr(self.ws),
+                                         self.ws.numel(), self.host, _lib.ptr(self.dev),
+                                         current_stream_ptr(self.device)), "dkg_plan_init")
         self.fused = bool(lib.dkg_plan_fused(self.host))  # forward_into is one fused launch
         self._fwd = lib.dkg_plan_forward
         self._fwd_batches = lib.dkg_plan_forward_batches
         self._fwd_timed = lib.dkg_plan_forward_timed
         self._fwd_grad_hostx = lib.dkg_plan_forward_grad_hostx
         self._dev_ptr = _lib.ptr(self.dev)
+
+    def _lead(self, *shape):
+        """The shape of a result: with a leading T axis on a plan of several targets."""
+        return shape if self.targets is None else (self._nt,) + shape
 
     def envelope_geometry(self) -> dict:
         """Which envelope kernel the plan launches (dkg_debug_plan_envelope; host only): ``slots`` (register
@@ -374,7 +412,8 @@ class ForwardPlan:
                                "the result is invalid")
 
     def forward_into(self, X: torch.Tensor, kg: torch.Tensor, kg_pairs=None) -> None:
-        """Hot path: X (device, B x d, contiguous fp64) -> kg (device, B)."""
+        """Hot path: X (device, B x d, contiguous fp64) -> kg (device, B; [T, B] on a plan of T targets, with
+        kg_pairs [T, B, S])."""
         st = self._fwd(self.host, self._dev_ptr, X.data_ptr(), X.shape[0], kg.data_ptr(),
                        0 if kg_pairs is None else kg_pairs.data_ptr(),
                        torch.cuda.current_stream(self.device).cuda_stream)
@@ -400,9 +439,9 @@ class ForwardPlan:
         B = X.shape[0]
         if B > self.max_B:
             raise ValueError(f"{B} candidates > plan capacity {self.max_B}")
-        kg = torch.empty(B, dtype=torch.double, device=self.device)
-        pairs = torch.empty(B, self.S, dtype=torch.double, device=self.device)
-        hull = torch.empty(B, self.S, dtype=torch.int32, device=self.device)
+        kg = torch.empty(self._lead(B), dtype=torch.double, device=self.device)
+        pairs = torch.empty(self._lead(B, self.S), dtype=torch.double, device=self.device)
+        hull = torch.empty(self._lead(B, self.S), dtype=torch.int32, device=self.device)
         self.forward_into(X, kg, pairs)
         _lib.check(_lib.load().dkg_plan_hull_sizes(self.host, _lib.ptr(hull), B, current_stream_ptr(self.device)),
                    "dkg_plan_hull_sizes")
@@ -431,8 +470,8 @@ class ForwardPlan:
         B = X.shape[0]
         if B > self.max_B:
             raise ValueError(f"{B} candidates > plan capacity {self.max_B}")
-        kg = torch.empty(B, dtype=torch.double, device=self.device)
-        dkg = torch.empty(B, self.state.d, dtype=torch.double, device=self.device)
+        kg = torch.empty(self._lead(B), dtype=torch.double, device=self.device)
+        dkg = torch.empty(self._lead(B, self.state.d), dtype=torch.double, device=self.device)
         _lib.check(_lib.load().dkg_plan_forward_grad(self.host, self._dev_ptr, _lib.ptr(X), B, _lib.ptr(kg),
                                                      _lib.ptr(dkg), current_stream_ptr(self.device)),
                    "dkg_plan_forward_grad")
@@ -458,7 +497,8 @@ class ForwardPlan:
         if B > self.max_B:
             raise ValueError(f"{B} candidates > plan capacity {self.max_B}")
         if B == 0:
-            return torch.empty(0, dtype=torch.double), torch.empty(0, d, dtype=torch.double)
+            return (torch.empty(self._lead(0), dtype=torch.double),
+                    torch.empty(self._lead(0, d), dtype=torch.double))
         if not graph and B * d <= _lib.DKG_XARG_MAX and torch.cuda.current_device() == self.device.index:
             return self._forward_grad_hostx(X_host, B, d)
         with torch.cuda.device(self.device):
@@ -472,16 +512,17 @@ class ForwardPlan:
         B = 1 L-BFGS-B path, with no reshape of X and the results copied out once through numpy (a torch
         slice or view costs about a microsecond of host time each, on a call whose device chain is ~30 us)."""
         d = self.state.d
-        if (self.grad and 0 < B <= self.max_B and B * d <= _lib.DKG_XARG_MAX
+        if (self.targets is None and self.grad and 0 < B <= self.max_B and B * d <= _lib.DKG_XARG_MAX
                 and torch.cuda.current_device() == self.device.index):
             r = self._forward_grad_hostx_raw(X_host, B, d)
             return torch.from_numpy(r[:B].reshape(kshape)), torch.from_numpy(r[B:].reshape(xshape))
         kg, dkg = self.forward_grad_host(X_host.reshape(B, d))
-        return kg.reshape(kshape), dkg.reshape(xshape)
+        return kg.reshape(self._lead(*kshape)), dkg.reshape(self._lead(*xshape))
 
     def _forward_grad_hostx(self, X_host: torch.Tensor, B: int, d: int):
         r = self._forward_grad_hostx_raw(X_host, B, d)
-        return torch.from_numpy(r[:B]), torch.from_numpy(r[B:].reshape(B, d))
+        n = self._nt * B
+        return torch.from_numpy(r[:n].reshape(self._lead(B))), torch.from_numpy(r[n:].reshape(self._lead(B, d)))
 
     def _forward_grad_hostx_raw(self, X_host: torch.Tensor, B: int, d: int):
         # the plan's device is current; one C call launches, lets the envelope kernel write the pinned
@@ -490,8 +531,9 @@ class ForwardPlan:
         if io is None:
             self._host_buffers(d)
             dx = self._dx[:B * d]
-            out = self._hout[:B * (d + 1)]
-            io = self._io[B] = (dx.data_ptr(), self._dout[:B].data_ptr(), self._dout[B:B * (d + 1)].data_ptr(),
+            n = self._nt * B  # [kg (T x B) | dKG/dx (T x B x d)]
+            out = self._hout[:n * (d + 1)]
+            io = self._io[B] = (dx.data_ptr(), self._dout[:n].data_ptr(), self._dout[n:n * (d + 1)].data_ptr(),
                                 out.data_ptr(), out.numpy())
         xc = X_host
         if xc.dtype != torch.double or not xc.is_contiguous():
@@ -506,9 +548,9 @@ class ForwardPlan:
         """The pinned host and device staging buffers of the host entries (made once, sized for max_B)."""
         if getattr(self, "_hx", None) is None:
             self._hx = torch.empty(self.max_B * d, dtype=torch.double).pin_memory()
-            self._hout = torch.empty(self.max_B * (d + 1), dtype=torch.double).pin_memory()
+            self._hout = torch.empty(self._nt * self.max_B * (d + 1), dtype=torch.double).pin_memory()
             self._dx = torch.empty(self.max_B * d, dtype=torch.double, device=self.device)
-            self._dout = torch.empty(self.max_B * (d + 1), dtype=torch.double, device=self.device)
+            self._dout = torch.empty(self._nt * self.max_B * (d + 1), dtype=torch.double, device=self.device)
             self._done = torch.cuda.Event()
             self._graphs = {}
             self._io = {}
@@ -518,7 +560,8 @@ class ForwardPlan:
         stream = torch.cuda.current_stream(self.device)
         self._host_buffers(d)
         dx = self._dx[:B * d].view(B, d)
-        kg, dkg = self._dout[:B], self._dout[B:B * (d + 1)].view(B, d)
+        n = self._nt * B
+        kg, dkg = self._dout[:n], self._dout[n:n * (d + 1)].view(n, d)
         lib = _lib.load()
 
         def launch(stream):
@@ -540,11 +583,11 @@ class ForwardPlan:
             g.replay()
         else:
             launch(stream.cuda_stream)
-        out = self._hout[:B * (d + 1)]
-        out.copy_(self._dout[:B * (d + 1)], non_blocking=True)
+        out = self._hout[:n * (d + 1)]
+        out.copy_(self._dout[:n * (d + 1)], non_blocking=True)
         self._done.record(stream)
         self._done.synchronize()
-        return out[:B].clone(), out[B:].view(B, d).clone()
+        return out[:n].clone().view(self._lead(B)), out[n:].clone().view(self._lead(B, d))
 
     def forward_host(self, X_host: torch.Tensor) -> torch.Tensor:
         """KG[B] for host candidates X (B x d) as a host tensor: one pinned H2D copy, the forward's launches
@@ -555,7 +598,7 @@ class ForwardPlan:
         if B > self.max_B:
             raise ValueError(f"{B} candidates > plan capacity {self.max_B}")
         if B == 0:
-            return torch.empty(0, dtype=torch.double)
+            return torch.empty(self._lead(0), dtype=torch.double)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device)
             self._host_buffers(d)
@@ -563,24 +606,24 @@ class ForwardPlan:
             hx.copy_(X_host.detach().reshape(B, d))
             dx = self._dx[:B * d].view(B, d)
             dx.copy_(hx, non_blocking=True)
-            kg = self._dout[:B]
+            kg = self._dout[:self._nt * B]
             st = self._fwd(self.host, self._dev_ptr, dx.data_ptr(), B, kg.data_ptr(), 0, stream.cuda_stream)
             if st:
                 _lib.check(st, "dkg_plan_forward")
-            out = self._hout[:B]
+            out = self._hout[:self._nt * B]
             out.copy_(kg, non_blocking=True)
             self._done.record(stream)
             self._done.synchronize()
             if self.fused:
                 self._check_handoffs()
-            return out.clone()
+            return out.clone().view(self._lead(B))
 
     def time_stage(self, X: torch.Tensor, stage: int, reps: int) -> float:
         """Average duration (ms) of ``reps`` back-to-back launches of one kernel
         (0 cross_root, 1 posterior_cov, 2 envelope; 3 the whole forward as ``forward_into`` launches it),
         HIP events on the launch stream."""
         X = X.detach().to(self.device, torch.double).contiguous()
-        kg = torch.empty(X.shape[0], dtype=torch.double, device=self.device)
+        kg = torch.empty(self._nt * X.shape[0], dtype=torch.double, device=self.device)
         ms = _lib.c_float()
         _lib.check(_lib.load().dkg_plan_time_stage(self.host, self._dev_ptr, _lib.ptr(X), X.shape[0], _lib.ptr(kg),
                                                    None, current_stream_ptr(self.device), stage, reps,
@@ -604,7 +647,7 @@ class ForwardPlan:
         B = X.shape[0]
         if B > self.max_B:
             raise ValueError(f"{B} candidates > plan capacity {self.max_B}")
-        kg = torch.empty(B, dtype=torch.double, device=self.device)
+        kg = torch.empty(self._lead(B), dtype=torch.double, device=self.device)
         if timed:
             ms = (_lib.c_float * 3)()
             _lib.check(self._fwd_timed(self.host, self._dev_ptr, _lib.ptr(X), B, _lib.ptr(kg), _lib.ptr(kg_pairs),

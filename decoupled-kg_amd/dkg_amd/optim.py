@@ -163,6 +163,69 @@ def optimize_acqf(acq_function: Callable[[Tensor], Tensor], bounds: Tensor, q: i
     return batch_candidates, batch_acq_values
 
 
+def joint_best_per_cost(kg: Tensor, costs) -> Tuple[Tensor, Tensor]:
+    """The decoupled decision at fixed candidates: ``kg [T, *batch]`` (row t: KG observing objective t alone)
+    -> ``(max_t max(KG_t, 0) / cost_t [*batch], the winning t [*batch])``.  ``_choose_best_objective``'s rule
+    per candidate: negative values clip to 0, ties go to the cheaper objective, then to the lower index."""
+    c = [float(x) for x in costs]
+    if kg.shape[0] != len(c):
+        raise ValueError(f"{kg.shape[0]} targets but {len(c)} costs")
+    best = kg[0].clamp_min(0) / c[0]
+    win = torch.zeros(kg.shape[1:], dtype=torch.long, device=kg.device)
+    wcost = torch.full(kg.shape[1:], c[0], dtype=kg.dtype, device=kg.device)
+    for t in range(1, len(c)):
+        v = kg[t].clamp_min(0) / c[t]
+        take = (v > best) | ((v == best) & (c[t] < wcost))
+        best = torch.where(take, v, best)
+        win = torch.where(take, torch.full_like(win, t), win)
+        wcost = torch.where(take, torch.full_like(wcost, c[t]), wcost)
+    return best, win
+
+
+class JointDecoupledAcquisition:
+    """``A(x) = max_t max(KG_t(x), 0) / cost_t`` over the m single-objective targets, as one acquisition for
+    ``optimize_acqf`` (``optimize_for_single_objective(joint=True)``).
+
+    ``acqs``: one acquisition with ``forward_targets`` / ``value_and_grad_host_targets`` (the device
+    ``DiscreteKnowledgeGradient``: every evaluation is one pass over the shared stages for all targets), or a
+    list of m acquisitions, one per objective, whose ``forward``s are combined (an injected acquisition
+    without the multi-target entries).  The gradient of A is the winning target's dKG/dx / cost where its KG
+    is positive, 0 where the clip holds."""
+
+    def __init__(self, acqs, costs, num_outputs: int):
+        self.m = int(num_outputs)
+        self.costs = [float(costs[i]) for i in range(self.m)]
+        self.targets = list(range(self.m))
+        self.acqs = acqs
+        self.shared = not isinstance(acqs, (list, tuple))
+        if not self.shared and len(acqs) != self.m:
+            raise ValueError(f"{len(acqs)} acquisitions for {self.m} objectives")
+        if self.shared and hasattr(acqs, "value_and_grad_host_targets"):
+            self.value_and_grad_host = self._value_and_grad_host  # gen_candidates_scipy's one-round-trip route
+
+    def per_target(self, X: Tensor) -> Tensor:
+        """KG_t(X) for every objective t: ``[m, *batch]``."""
+        if self.shared:
+            return self.acqs.forward_targets(X, targets=self.targets)
+        return torch.stack([a(X) for a in self.acqs])
+
+    def __call__(self, X: Tensor) -> Tensor:
+        kg = self.per_target(X)
+        _, win = joint_best_per_cost(kg.detach(), self.costs)
+        c = torch.tensor(self.costs, dtype=kg.dtype, device=kg.device)
+        return kg.gather(0, win.unsqueeze(0)).squeeze(0).clamp_min(0) / c[win]
+
+    def _value_and_grad_host(self, X: Tensor):
+        kg, dkg = self.acqs.value_and_grad_host_targets(X, targets=self.targets)  # [m, *batch], [m, *X.shape]
+        best, win = joint_best_per_cost(kg, self.costs)
+        c = torch.tensor(self.costs, dtype=kg.dtype)
+        kw = kg.gather(0, win.unsqueeze(0)).squeeze(0)
+        idx = win.reshape((1,) + tuple(win.shape) + (1,) * (dkg.dim() - 1 - win.dim())).expand((1,) + dkg.shape[1:])
+        scale = torch.where(kw > 0, 1.0 / c[win], torch.zeros_like(kw))
+        g = dkg.gather(0, idx).squeeze(0) * scale.reshape(tuple(scale.shape) + (1,) * (dkg.dim() - 1 - win.dim()))
+        return best, g
+
+
 def _get_standard_bounds(dim: int, dtype=torch.double) -> Tensor:
     """``acquisition_optimisation_strategy.py:555``: the unit cube."""
     return torch.stack([torch.zeros(dim, dtype=dtype), torch.ones(dim, dtype=dtype)])
@@ -208,13 +271,41 @@ class DiscreteKgOptimisationSpec:
                                          target_output_ix=target, device=self.device)
 
     def optimize_for_single_objective(self, model, costs: Union[Tensor, Sequence], input_dim: int, *,
-                                      scalarisation_weights: Tensor, **_unused_kwargs) -> Tuple[Tensor, int, Tensor]:
-        """Decoupled KG per objective, best KG per cost (:196-240)."""
+                                      scalarisation_weights: Tensor, joint: bool = False,
+                                      **_unused_kwargs) -> Tuple[Tensor, int, Tensor]:
+        """Decoupled KG per objective, best KG per cost (:196-240).
+
+        ``joint=True`` (not the reference's search; opt-in): one ``optimize_acqf`` run on
+        ``A(x) = max_t max(KG_t(x), 0) / cost_t`` (``JointDecoupledAcquisition``) instead of one run per
+        objective.  In exact arithmetic the maximum of A is the reference's decision -- the best objective's
+        best point per cost -- but the local search differs: one set of raw samples and restarts follows the
+        upper envelope of the m scaled surfaces, where the reference gives every objective its own restarts.
+        On the device KG every evaluation is one pass over the shared cross and covariance stages for all m
+        targets (``value_and_grad_host_targets``).  Returns the same triple."""
         from .discretekg import _as_model_state
 
         standard_bounds = _get_standard_bounds(input_dim)
+        m = _as_model_state(model).num_outputs
+        if joint:
+            # the device KG evaluates every target on one acquisition; an injected acquisition without
+            # value_and_grad_host_targets is built once per objective and combined from the m forwards
+            acqs = self._acq(model, input_dim, scalarisation_weights, 0)
+            if not hasattr(acqs, "value_and_grad_host_targets"):
+                acqs = [acqs] + [self._acq(model, input_dim, scalarisation_weights, i) for i in range(1, m)]
+            acq_func = JointDecoupledAcquisition(acqs, costs, m)
+            candidate_x, _ = optimize_acqf(acq_function=acq_func, bounds=standard_bounds, q=1,
+                                           num_restarts=self.num_restarts, raw_samples=self.raw_samples,
+                                           options=self._options())
+            candidate_x = candidate_x.detach()
+            with torch.no_grad():
+                kg = acq_func.per_target(candidate_x.unsqueeze(0)).reshape(m)
+            best_i = int(joint_best_per_cost(kg, acq_func.costs)[1])
+            if kg[best_i] < 0:
+                logger.warning("Optimal acquisition function value is negative: obj_index=%i, acq_value=%f", best_i,
+                               kg[best_i])
+            return candidate_x, best_i, (kg[best_i] / acq_func.costs[best_i]).detach()
         candidates = []
-        for i in range(_as_model_state(model).num_outputs):
+        for i in range(m):
             acq_func = self._acq(model, input_dim, scalarisation_weights, i)
             candidate_x, acq_value = optimize_acqf(acq_function=acq_func, bounds=standard_bounds, q=1,
                                                    num_restarts=self.num_restarts, raw_samples=self.raw_samples,

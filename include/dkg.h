@@ -259,6 +259,25 @@ size_t dkg_plan_workspace(const dkg_output* outs, int m, int d, int N, int max_B
 int dkg_plan_init(const dkg_output* outs, int m, int d, const double* disc, int N, const double* weights, int S,
                   int target, int max_B, int flags, void* workspace, size_t workspace_bytes, void* host_plan,
                   void* dev_plan, void* stream);
+/* A plan of T targets: `targets` (host, [T]) holds 1 <= T <= m + 1 distinct entries in [-1, m), -1 = all
+ * outputs observed; anything else is DKG_ERR_ARG.  The cross and covariance stages do not depend on the
+ * target, so every call on the plan runs them once and the envelope once per (target, candidate): row
+ * (tau, b) of a result has exactly the bits a single-target plan of targets[tau] writes for candidate b.
+ *   dkg_plan_forward             kg[tau*B + b], kg_pairs[tau][b][S]
+ *   dkg_plan_hull_sizes          out[tau][b][S]
+ *   dkg_plan_forward_grad        kg[tau*B + b], dkg_dx[tau][b][d]
+ *   dkg_plan_forward_grad_hostx  the same (B * d <= DKG_XARG_MAX: the candidates are shared); out_host holds
+ *                                T * B * (d + 1) doubles [kg | dkg_dx]
+ *   dkg_plan_forward_timed, dkg_plan_time_stage   kg holds T * B doubles
+ *   dkg_plan_lines               the lines of targets[0]
+ * DKG_PLAN_F32 plans are accepted (forward only, as with one target).  DKG_PLAN_FUSED with T > 1 and
+ * dkg_plan_forward_batches / dkg_plan_time_stage_batches on a plan of T > 1 return DKG_ERR_UNSUPPORTED.
+ * dkg_plan_init is the T = 1 case and dkg_plan_workspace_targets(T = 1) equals dkg_plan_workspace; the
+ * workspace grows with T by the per-item result buffers only (0 for T outside 1..m + 1). */
+size_t dkg_plan_workspace_targets(const dkg_output* outs, int m, int d, int N, int max_B, int S, int T, int flags);
+int dkg_plan_init_targets(const dkg_output* outs, int m, int d, const double* disc, int N, const double* weights,
+                          int S, const int* targets, int T, int max_B, int flags, void* workspace,
+                          size_t workspace_bytes, void* host_plan, void* dev_plan, void* stream);
 /* kg[b] (and kg_pairs[b x S], nullable) for B <= max_B candidates xnew (device, B x d);
  * same result as dkg_forward with the plan's arguments.  One fused launch for a plan built
  * with DKG_PLAN_FUSED (a call given kg_pairs runs the three stages). */
