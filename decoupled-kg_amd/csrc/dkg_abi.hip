@@ -132,7 +132,7 @@ WsLayout layout(const dkg_output* outs, int m, int N, int B, int S, int d = 0, i
     L.var[i] = L.var_all + (size_t)i * Bp * sizeof(double);
   }
   int sw, split;
-  envelope_geometry(std::max(B, 1), std::max(S, 1), &sw, &split, !(flags & DKG_PLAN_FUSED));
+  envelope_geometry(std::max(S, 1), &sw, &split);
   // split > 1: every pair's KG (and, value+gradient, its dKG/dx) for the last workgroup's ordered sums
   const size_t pcols = (size_t)std::max(S, 1) + pair_groups(std::max(S, 1));  // pair values + group terms
   L.wg_part = off;
@@ -145,7 +145,7 @@ WsLayout layout(const dkg_output* outs, int m, int N, int B, int S, int d = 0, i
   off = align256(off + Bp * sizeof(int));
   L.hull_pairs = off;
   off = align256(off + items * std::max(S, 1) * sizeof(int));
-  if (N + 1 <= 64 * 33) {  // the staged forward's intercept cache (Plan::icpt)
+  if (N + 1 <= 64 * 33) {  // staged forward: intercepts_kernel's scratch (Plan::icpt) and its results (itop / itopk)
     L.icpt = off;
     off = align256(off + (size_t)std::max(S, 1) * 64 * env_slots(N + 1) * sizeof(double));
     L.itop = off;
@@ -205,7 +205,7 @@ int build_plan(const dkg_output* outs, int m, int d, const double* disc, int N, 
   if (target < -1 || target >= m) return fail(DKG_ERR_ARG, "target_output_ix=%d out of range for %d outputs", target, m);
   if (N > (1 << 22)) return fail(DKG_ERR_UNSUPPORTED, "N=%d discretisation points (supported <= %d)", N, 1 << 22);
   int sw, split;
-  envelope_geometry(std::max(max_B, 1), S, &sw, &split, !(flags & DKG_PLAN_FUSED));
+  envelope_geometry(S, &sw, &split);
   int max_np = 16;
   for (int i = 0; i < m; ++i) max_np = std::max(max_np, pad16(outs[i].n));
   // the envelope stages the line data in LDS when it fits and the lines fit
@@ -281,7 +281,7 @@ int build_plan(const dkg_output* outs, int m, int d, const double* disc, int N, 
   P->dup = reinterpret_cast<int*>(ws + L.dup);
   P->wg_gpart = reinterpret_cast<double*>(ws + L.wg_gpart);
   P->hull_pairs = reinterpret_cast<int*>(ws + L.hull_pairs);
-  // the intercept cache serves the staged forward envelope (a gradient plan's forward included)
+  // each scalarisation's top intercept serves the staged forward envelope (a gradient plan's forward included)
   if (L.icpt && !stream) {
     P->icpt = reinterpret_cast<double*>(ws + L.icpt);
     P->icpt_stride = 64 * env_slots(N + 1);

@@ -393,15 +393,6 @@ __device__ __forceinline__ double readlane_f64(double v, int l);
 
 // A wave-uniform double moved to SGPRs (v_readfirstlane of both halves), so
 // it takes no VGPRs while it stays live.
-// A wave-uniform pointer to global memory, held in SGPRs: loads from it take the scalar-base form
-// (global_load ... v_offset, s[base]) with one VGPR offset, instead of a 64-bit VGPR address per load.
-typedef const __attribute__((address_space(1))) double* gdptr;
-__device__ __forceinline__ gdptr uniform_gptr(const double* p) {
-  const uint64_t u = reinterpret_cast<uint64_t>(p);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-  return reinterpret_cast<gdptr>(((uint64_t)hi << 32) | lo);
-}
-
 __device__ __forceinline__ double sgpr_f64(double v) {
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)),
                           __builtin_amdgcn_readfirstlane(__double2loint(v)));
@@ -499,20 +490,10 @@ __device__ __forceinline__ double psi(double c) {
 // share its L2 -- the outputs of one covariance block write the same line records (whole records leave L2
 // instead of one component per write-back), the workgroups of one candidate's envelope read the same
 // records (one HBM read instead of one per workgroup).  False for the padding ids (blk >= nblk).
-// DKG_XCD_GROUP=0 (A/B only: profiles/r04/abv, 9.95 against 10.2 M KG-evals/s with four forwards in flight): the ids
-// follow the 2-D order (member-major, blk = L % nblk), every block's members on different XCDs.
-#ifndef DKG_XCD_GROUP
-#define DKG_XCD_GROUP 1
-#endif
-__host__ __device__ inline int xcd_group_size(int nblk, int groups) {
-  return DKG_XCD_GROUP ? 8 * groups * ((nblk + 7) / 8) : nblk * groups;
-}
+// (The 2-D order -- member-major, blk = L % nblk, every block's members on different XCDs -- gave 9.95 against
+// 10.2 M KG-evals/s with four forwards in flight: profiles/r04/abv.)
+__host__ __device__ inline int xcd_group_size(int nblk, int groups) { return 8 * groups * ((nblk + 7) / 8); }
 __device__ __forceinline__ bool xcd_group(int L, int nblk, int groups, int& blk, int& member) {
-  if (!DKG_XCD_GROUP) {
-    blk = L % nblk;
-    member = L / nblk;
-    return true;
-  }
   const int r = L >> 3;
   member = r % groups;
   blk = (r / groups) * 8 + (L & 7);

@@ -63,25 +63,8 @@ __device__ __forceinline__ unsigned long long* kst_slot(int dst, const Plan* P, 
 // multiplication); the hull edges are collected one per lane and psi is
 // evaluated for all of them at once.
 constexpr int ENV_CAP = 128;
-#ifndef DKG_ENV_REFINE
-#define DKG_ENV_REFINE 1
-#endif
-#ifndef DKG_REFINE_OVERFLOW  // a list past ENV_CAP filtered against the chain of its entries
-#define DKG_REFINE_OVERFLOW 1
-#endif
 constexpr int HCAP = 128;  // GRAD: queued envelope lines per wave before their gradient terms are flushed
 constexpr int STREAM_CHUNK = 16;  // register slots per streamed chunk (1024 lines)
-// Staged forward: the intercepts from the plan's per-scalarisation cache (Plan::icpt) instead of the staged
-// mu_D records.  Off by default: the cache rows cost each wave 17 global loads per pair, and the envelope
-// was slower with them (profiles/r04/ab: 10.6 -> 11.0 us alone, 11.5 -> 9.9 M KG-evals/s with 4 streams).
-#ifndef DKG_ICP
-#define DKG_ICP 0
-#endif
-// The staged forward takes T (max a, tie: min b) from the plan's per-scalarisation top intercept when that
-// decides it (TopHint), instead of two wave reductions.
-#ifndef DKG_TOP_HINT
-#define DKG_TOP_HINT 1
-#endif
 // Streaming forward with LDS-staged chunks (M = 2..4): the extremes and filter passes read the line
 // records from LDS, STAGED_SLOTS * 64 lines per chunk, double-buffered and shared by the workgroup's pairs.
 constexpr int STAGED_SLOTS = 8;
@@ -551,21 +534,16 @@ struct TopHint {
   double aT, bT;
 };
 
-template <int MAXL, class Build, class Build0 = int>
+template <int MAXL, class Build>
 __device__ __forceinline__ EdgeSum env_pair_regs_edges(Build&& build, int nl, int lane, double* sb, double* sa, int* si,
                                                 bool force_walk, int* nhull, const WalkOut* out = nullptr,
                                                 unsigned long long* pst = nullptr, bool flat_ok = false,
-                                                const Build0* build0 = nullptr,
                                                 TopHint hint = TopHint{false, 0.0, 0.0}) {
   FwdEnv f;
   if (pst) pst[0] = __builtin_amdgcn_s_memtime();
   {
     double la[MAXL], lb[MAXL];
-    if constexpr (std::is_same_v<Build0, int>) {
-      build(la, lb);
-    } else {
-      (*build0)(la, lb);  // the first build (e.g. from registers loaded ahead)
-    }
+    build(la, lb);
     if (pst) pst[1] = __builtin_amdgcn_s_memtime();
     if (flat_ok && hint.valid) {
       f.aT = hint.aT;  // what env_top finds, without its two wave reductions
@@ -609,13 +587,13 @@ __device__ __forceinline__ EdgeSum env_pair_regs_edges(Build&& build, int nl, in
   }
   // opaque copies of the chain ends: no term of the first filter's chords is kept live for the later filters
   asm volatile("" : "+v"(f.bL), "+v"(f.aL), "+v"(f.bT), "+v"(f.aT), "+v"(f.bR), "+v"(f.aR));
-  if (DKG_ENV_REFINE && f.cnt > ENV_REFINE_MIN && !force_walk) {  // wave-uniform: the chain L, V1, T, V2, R
+  if (f.cnt > ENV_REFINE_MIN && !force_walk) {  // wave-uniform: the chain L, V1, T, V2, R
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     if (f.cnt <= ENV_CAP) {
       f.cnt = env_refine_list(f.cnt, lane, sb, sa, si, f);
-    } else if (DKG_REFINE_OVERFLOW) {
+    } else {  // a list past ENV_CAP filtered against the chain of its entries:
       // the chain of the entries the list holds (lines of the set), then the lines filtered against it in
       // two halves: slopes <= bT against the chords L-V1, V1-T, the rest against T-V2, V2-R (the largest
       // height of a line above the chain is at the breakpoint its slope brackets), each half in line order
@@ -681,14 +659,13 @@ __device__ __forceinline__ EdgeSum env_pair_regs_edges(Build&& build, int nl, in
 }
 
 // KG_w of register-held lines (env_pair_regs_edges), with the single psi evaluation of its edge terms.
-template <int MAXL, class Build, class Build0 = int>
+template <int MAXL, class Build>
 __device__ __forceinline__ double env_pair_regs(Build&& build, int nl, int lane, double* sb, double* sa, int* si,
                                                 bool force_walk, int* nhull, const WalkOut* out = nullptr,
                                                 unsigned long long* pst = nullptr, bool flat_ok = false,
-                                                const Build0* build0 = nullptr,
                                                 TopHint hint = TopHint{false, 0.0, 0.0}) {
   return finish_edges(
-      env_pair_regs_edges<MAXL>(build, nl, lane, sb, sa, si, force_walk, nhull, out, pst, flat_ok, build0, hint));
+      env_pair_regs_edges<MAXL>(build, nl, lane, sb, sa, si, force_walk, nhull, out, pst, flat_ok, hint));
 }
 
 // ---------------------------------------------------------------------------
@@ -1242,7 +1219,7 @@ __device__ __forceinline__ void stream_keep(const double (&la)[MAXL], const doub
 }
 
 // ---------------------------------------------------------------------------
-// Staged streaming forward, one pass (DKG_STG_SAMPLE): the survivor list is filtered against a chain of
+// Staged streaming forward, one pass: the survivor list is filtered against a chain of
 // lines of the set (the quickhull vertices of a strided sample of the pair's lines) instead of the chords
 // L-T / T-R of the exact extremes, which took a pass of their own.
 //
@@ -1254,9 +1231,6 @@ __device__ __forceinline__ void stream_keep(const double (&la)[MAXL], const doub
 // at least tau_c below H at its slope, so below the envelope by at least rel W everywhere: the guard argument
 // of DESIGN.md 4.3 holds for the walk over the list as for the two-chord list.  Every line of H (L, T, R
 // with their tie rules included) passes, so the list's own extremes are the set's.
-#ifndef DKG_STG_SAMPLE
-#define DKG_STG_SAMPLE 1
-#endif
 #ifndef DKG_SH_ROUNDS
 #define DKG_SH_ROUNDS 1
 #endif
@@ -1548,11 +1522,8 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
   constexpr int MP = cov_rec(M);  // doubles per line record
   const int SLp = STREAM ? 0 : stage_stride(N, MP);
   constexpr int LC = list_cap(STREAM && !GRAD);  // survivor-list capacity per wave
-  // (the staged forward without mu_D records: its covariance records start where they would)
-  constexpr bool ICP = DKG_ICP && !GRAD && !STREAM && !HO;  // intercepts from the plan's cache (Plan::icpt)
-  constexpr bool MU_STAGED = !ICP;
   double* lmu = smem + STAGE_FRONT;
-  double* lcv = lmu + ((STREAM || MU_STAGED) ? SLp : 0);
+  double* lcv = lmu + SLp;
   double* lw = lcv + SLp;
   double* skg = lw + ((S * m + 1) & ~1);  // KG_j of the group's pairs (summed in j order)
   double* sbuf = skg + ((S + 1) & ~1);
@@ -1605,8 +1576,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
   }
   const double* wsrc = wts;
   if constexpr (!STREAM) {
-    // (the staged forward reads its intercepts from the plan's cache instead: no mu_D records in LDS)
-    if constexpr (MU_STAGED) dma_to_lds(mu_src[0], lmu, N * MP, wave, SW, lane_k);
+    dma_to_lds(mu_src[0], lmu, N * MP, wave, SW, lane_k);
     if constexpr (!HO) dma_to_lds(cv_src[0], lcv, N * MP, wave, SW, lane_k);
   }
   if constexpr (GRAD) {
@@ -1630,7 +1600,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
   // this wave's scalarisation's top intercept over k >= 1 (TopHint), read with the first batch
   double hA1 = 0.0;
   int hk1 = 0, hc1 = 0;
-  constexpr bool HINT = DKG_TOP_HINT && !GRAD && !STREAM && !HO;
+  constexpr bool HINT = !GRAD && !STREAM && !HO;
   if constexpr (HINT) {
     if (P->itop != nullptr) {
       const int jh = min(g * SW + wave, S - 1);
@@ -1679,26 +1649,13 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
   const int pad_end = (64 * MAXL - 1) * MP;
   auto pad_lines = [&](int lo, int hi) {  // doubles lo .. hi-1 of both record arrays
     for (int e = lo + (int)threadIdx.x; e < hi; e += blockDim.x) {
-      if constexpr (MU_STAGED) lmu[e] = __builtin_nan("");
+      lmu[e] = __builtin_nan("");
       lcv[e] = __builtin_nan("");
     }
   };
   if constexpr (!STREAM) pad_lines(max(N * MP, SLd), pad_end);
   // pairs j0 .. j1-1 of the candidate, one per wave (gridDim.y = ceil(S / SW), envelope_geometry)
   const int j0 = g * SW, j1 = min(S, j0 + SW);
-  // Staged forward with the plan's intercept cache (Plan::icpt): this wave's intercepts a_k (slot t of lane
-  // l: line l + 64 t) straight into registers, in flight with the staging DMA; only the covariance records
-  // are built from LDS.
-  gdptr icp = nullptr;  // this wave's row of the cache (wave-uniform)
-  double ila[ICP ? MAXL : 1];
-  if constexpr (ICP) {
-    // always set for a staged plan (dkg_abi.hip build_plan)
-    icp = uniform_gptr(P->icpt + (size_t)min(j0 + wave, S - 1) * P->icpt_stride);
-    if (j0 + wave < j1) {
-#pragma unroll
-      for (int t = 0; t < MAXL; ++t) ila[t] = icp[lane_k + 64 * t];
-    }
-  }
   if (!GRAD) KST(st, 2);  // GRAD stamps: 2 preamble done, 3 filter, 4 hull, 5 gradient flush (first pair)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -1887,7 +1844,6 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
         lb[0] = (lane == 0) ? bb0 : lb[0];
       }
     };
-#if DKG_STG_SAMPLE
     // pass 0: the pair's sample hull.  Every stride-th line (line j * stride in slot j of a staged chunk laid
     // out as chunk 0) staged in buffer 0 by one strided DMA, then per wave the sample's extremes and
     // SH_ROUNDS quickhull rounds in registers; the vertex chain (lines of the set) goes to buffer 1.
@@ -1969,58 +1925,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
     // streamed lines (overflow path)
     if (!chain_ok) scnt = LIST_CAP_STREAM + 1;
     sf.status = 0;
-#else
-    // pass 1: extremes
-    ExtAcc e;
-#ifdef DKG_STG_STAMPS
-    unsigned long long twait = 0, tw0 = 0;
-#define STG_W0 tw0 = __builtin_amdgcn_s_memtime();
-#define STG_W1 twait += __builtin_amdgcn_s_memtime() - tw0;
-#else
-#define STG_W0
-#define STG_W1
-#endif
-    stage(0);
-    for (int q = 0; q < nq; ++q) {
-      STG_W0
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();  // chunk q landed; every wave is done with the other buffer
-      STG_W1
-      if (q + 1 < nq) stage(q + 1);
-      if (has) {
-        double la[CS], lb[CS];
-        build_staged(q, la, lb);
-        ext_fold<CS>(la, lb, q * SCH, NL, lane, e);
-      }
-    }
-    sf = ext_reduce(e);
-    // pass 2: the chord filter into the survivor list
-    const bool live = has && sf.status == 0;
-    const EnvChords ch = env_chords(sf.bL, sf.aL, sf.bT, sf.aT, sf.bR, sf.aR);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();  // every wave is done with the last chunk of pass 1
-    stage(0);
-    for (int q = 0; q < nq; ++q) {
-      STG_W0
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      STG_W1
-      if (q + 1 < nq) stage(q + 1);
-      if (live) {
-        double la[CS], lb[CS];
-        build_staged(q, la, lb);
-        stream_keep<CS>(la, lb, q * SCH, NL, ch, lane, sb, sa, sif, scnt);
-      }
-    }
-    __syncthreads();  // the chunk buffers are the refinement's vertex arrays from here
-#ifdef DKG_STG_STAMPS
-    if (st) st[4] = twait;  // raw: wait cycles of wave 0 over both passes
-    if (st) st[5] = __builtin_amdgcn_s_memtime();
-#endif
-#endif  // DKG_STG_SAMPLE
   }
-#undef STG_W0
-#undef STG_W1
 
   if (const int j = j0 + wave; j < j1) {
     const int lane = lane_k;
@@ -2403,14 +2308,12 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
       if (lane == 0)
         for (int dd = 0; dd < d; ++dd) gw[dd] = 0.0;
     } else if constexpr (STG) {
-#if DKG_STG_SAMPLE
       // L, T, R and the short-circuit test from the list (it holds every upper-hull line of the set), or,
       // after an overflow, from the streamed lines
       sf = (scnt <= LIST_CAP_STREAM) ? list_extremes(scnt, lane, sb, sa) : env_extremes_stream<MAXL>(nch, NL, lane,
                                                                                                      build_chunk);
 #ifdef DKG_STG_STAMPS
       if (lane == 0) P->hull_pairs[iw * S + j] = scnt;  // diagnostics build: the list length per pair
-#endif
 #endif
       if (sf.status == 1) {
         kgj = 0.0;
@@ -2465,62 +2368,10 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
           hint = TopHint{true, A1, bk};
         }
       }
-      if constexpr (ICP) {
-        // intercepts from the plan (first build: the registers loaded ahead; a rebuild: global memory)
-        auto slopes = [&](double (&lb)[MAXL]) {
-          const double* cvr = lcv + (lane - 1) * MP;
-          if (full) {
-#pragma unroll
-            for (int t = 0; t < MAXL; ++t) {
-              double acc = 0.0;  // build_lines' rec_dot of the covariance record
-              if constexpr (MP == 1) {
-                acc = fma(wb[0], cvr[64 * MP * t], acc);
-              } else {
-#pragma unroll
-                for (int q = 0; 2 * q < M; ++q) {
-                  const double2 u = *reinterpret_cast<const double2*>(cvr + 64 * MP * t + 2 * q);
-                  acc = fma(wb[2 * q], u.x, acc);
-                  if (2 * q + 1 < M) acc = fma(wb[2 * q + 1], u.y, acc);
-                }
-              }
-              lb[t] = acc;
-            }
-          } else {
-            double wbt = 0.0;
-#pragma unroll
-            for (int i = 0; i < M; ++i) wbt = (i == target) ? wb[i] : wbt;
-#pragma unroll
-            for (int t = 0; t < MAXL; ++t) lb[t] = wbt * cvr[64 * MP * t + target];
-          }
-          double a = a_off, bb = 0.0;  // line 0: the candidate itself (discretekg.py:182-183)
-#pragma unroll
-          for (int i = 0; i < M; ++i) {
-            a = fma(wa[i], l0m[i], a);
-            bb = fma(wb[i], l0v[i], bb);
-          }
-          lb[0] = (lane == 0) ? bb : lb[0];
-          return a;
-        };
-        auto first = [&](double (&la)[MAXL], double (&lb)[MAXL]) {
-          const double a0 = slopes(lb);
-#pragma unroll
-          for (int t = 0; t < MAXL; ++t) la[t] = ila[t];
-          la[0] = (lane == 0) ? a0 : la[0];
-        };
-        auto again = [&](double (&la)[MAXL], double (&lb)[MAXL]) {
-          const double a0 = slopes(lb);
-#pragma unroll
-          for (int t = 0; t < MAXL; ++t) la[t] = icp[lane + 64 * t];
-          la[0] = (lane == 0) ? a0 : la[0];
-        };
-        kgj = env_pair_regs<MAXL>(again, NL, lane, sb, sa, sif, force_walk, &hn, nullptr, pst, flat_ok, &first, hint);
-      } else {
-        // the lines are rebuilt from the staged LDS data if the list walk cannot finish,
-        // so no register line is live across it
-        auto rebuild = [&](double (&la)[MAXL], double (&lb)[MAXL]) { build_lines(la, lb); };
-        kgj = env_pair_regs<MAXL>(rebuild, NL, lane, sb, sa, sif, force_walk, &hn, nullptr, pst, flat_ok,
-                                  static_cast<const int*>(nullptr), hint);
-      }
+      // the lines are rebuilt from the staged LDS data if the list walk cannot finish,
+      // so no register line is live across it
+      auto rebuild = [&](double (&la)[MAXL], double (&lb)[MAXL]) { build_lines(la, lb); };
+      kgj = env_pair_regs<MAXL>(rebuild, NL, lane, sb, sa, sif, force_walk, &hn, nullptr, pst, flat_ok, hint);
     }
     if (pairs_out != nullptr && lane == 0) {
       pairs_out[ib * S + j] = kgj;

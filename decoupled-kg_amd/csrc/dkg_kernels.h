@@ -34,10 +34,7 @@ constexpr int DUP_NONE = 0x7fffffff;
 // kernel over the columns its wider tile needs: at n = 1024 (64 tiles, 32 groups) each entry ~24 times,
 // which took most of the stage.  At the headline's n = 256 the extra launch costs more than it saves
 // (profiles/r02/r02zz).
-#ifndef DKG_CROSS_KFILL
-#define DKG_CROSS_KFILL 1
-#endif
-__host__ __device__ inline bool cross_kfill(int np) { return DKG_CROSS_KFILL && np >= 512; }
+__host__ __device__ inline bool cross_kfill(int np) { return np >= 512; }
 // Launches over many candidates (a launch of several forward batches, dkg_plan_forward_batches) fill K(x, X)
 // once with the separate kernel at any n: the fill replicated over the column-pair groups of a row tile (~4.5x
 // at n = 256) is then work the whole device waits on, not latency one forward hides.  Same bits either way.
@@ -48,7 +45,7 @@ __host__ __device__ inline bool cross_kfill(int np) { return DKG_CROSS_KFILL && 
 #endif
 constexpr int KFILL_MIN_B = DKG_KFILL_MIN_B;
 __host__ __device__ inline bool cross_kfill_launch(int np, int B) {
-  return DKG_CROSS_KFILL && (np >= 512 || B >= KFILL_MIN_B);
+  return np >= 512 || B >= KFILL_MIN_B;
 }
 
 // Register slots per lane for a staged (non-streaming) line set of `lines`
@@ -102,10 +99,12 @@ struct Plan {
   int* sync_err;                    // fused waits that gave up (bits), after the counters
   size_t sync_bytes;                // bytes of the counter block (sync .. sync_err), a multiple of 16
   // Staged forward: the intercepts of lines k >= 1 depend on the weights and mu_D only, not on the
-  // candidates -- a_k = a_off + sum_i w_i sd_i mu_i(z_k), discretekg.py:201-213 -- so the plan keeps them
-  // (dkg_plan_init, the envelope's own arithmetic: bit-identical lines) beside each scalarisation's largest.
+  // candidates -- a_k = a_off + sum_i w_i sd_i mu_i(z_k), discretekg.py:201-213 -- so the plan keeps each
+  // scalarisation's largest (itop / itopk; dkg_plan_init, the envelope's own arithmetic: bit-identical lines).
+  // icpt is intercepts_kernel's scratch: it writes every a_k there and reads them back to find itop and itopk;
+  // no other kernel reads it (the envelope stages mu_D and forms its intercepts itself).
   double* icpt;                     // [S][icpt_stride]: slot k = a_k for 1 <= k <= N, NaN at k = 0 and k > N
-  int32_t icpt_stride;              // 64 * env_slots(N + 1): one entry per register slot of the envelope
+  int32_t icpt_stride;              // 64 * env_slots(N + 1): doubles per scalarisation in icpt
   double* itop;                     // [S]: max_{k >= 1} a_k (-inf when N = 0)
   int* itopk;                       // [S][2]: the first k >= 1 attaining it, and how many lines do
   float* kx32[DKG_MAX_OUTPUTS];     // F32 with the K(x, X) fill: kx's entries quad-packed in fp32 (frag32_index),
@@ -256,12 +255,12 @@ long long cross_tall_launches();
 bool cross_tall_eligible(int max_np, int d, int B, bool f32);
 hipError_t launch_debug_mfma(const double* a, const double* b, double* c, hipStream_t s);
 
-// Launch geometry of the envelope stage for (B, S): waves per workgroup and
+// Launch geometry of the envelope stage for S scalarisation pairs: waves per workgroup and
 // workgroups per candidate.
-void envelope_geometry(int B, int S, int* waves_per_wg, int* split, bool narrow);
-// mu: the mu_D records are staged too (the gradient and fused envelopes; the staged forward reads the plan's
-// intercept cache instead)
-size_t envelope_lds_bytes(int m, int N, int waves, int S, bool stream, bool grad = false, bool mu = true);
+void envelope_geometry(int S, int* waves_per_wg, int* split);
+// Dynamic LDS bytes of the envelope kernels.  Not streaming: the covariance records and the mu_D records are
+// both staged (forward, gradient and fused envelopes alike).
+size_t envelope_lds_bytes(int m, int N, int waves, int S, bool stream, bool grad = false);
 size_t cross_root_lds_bytes(int np, int d);
 
 }  // namespace dkg

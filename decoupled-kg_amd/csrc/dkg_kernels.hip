@@ -383,9 +383,9 @@ size_t cross_root_lds_bytes(int np, int d) { return cross_lds_doubles(np, d, cro
 
 static int outputs_bucket(int m) { return m <= 1 ? 1 : m <= 2 ? 2 : m <= 3 ? 3 : m <= 4 ? 4 : 8; }
 
-size_t envelope_lds_bytes(int m, int N, int waves, int S, bool stream, bool grad, bool mu) {
+size_t envelope_lds_bytes(int m, int N, int waves, int S, bool stream, bool grad) {
   const int M = outputs_bucket(m);
-  const size_t staged = stream ? 0 : (mu ? 2 : 1) * (size_t)stage_stride(N, cov_rec(M));
+  const size_t staged = stream ? 0 : 2 * (size_t)stage_stride(N, cov_rec(M));  // the covariance and mu_D records
   const bool refine = stream && !grad;  // streaming forward: long lists + quickhull vertex arrays
   const size_t lc = list_cap(refine);
   // per wave: the list (slopes, intercepts; forward: line indices) and the streaming vertex arrays
@@ -828,26 +828,15 @@ static hipError_t launch_cross_cov_t(const Plan& h, const Plan* dev, const doubl
                : launch_cross_cov_tt<DM, double>(h, dev, xnew, B, kg, s, stage, geom_B);
 }
 
-// Narrow small-batch geometry: off (DKG_ENV_NARROW=0).  At B = 1 its 16 one-wave workgroups staged the lines
-// 16 times and met in per-group tickets: the value+gradient envelope took 16.6 us against 14.1 us for two
-// 8-wave workgroups (profiles/r04/b1).
-#ifndef DKG_ENV_NARROW
-#define DKG_ENV_NARROW 0
-#endif
-void envelope_geometry(int B, int S, int* waves_per_wg, int* split, bool narrow) {
+void envelope_geometry(int S, int* waves_per_wg, int* split) {
   // Up to 8 scalarisation waves of one candidate per workgroup, one pair per
   // wave; with S <= 16 at most two workgroups per candidate, whose group sums
   // meet in one commutative atomic add (no inter-workgroup fences).
-  // Small batches (narrow): fewer waves per workgroup until the launch has at least ENV_MIN_WGS
-  // workgroups, so a B = 1 value+gradient call (the reference's optimize_acqf shape, batch_limit 1)
-  // spreads its S pairs over S CUs, one wave per SIMD, instead of two workgroups; the workgroups of
-  // one group of 8 pairs meet in ordered per-pair values (envelope_body: the same bits as the wide launch).
-  constexpr int ENV_MIN_WGS = 128;
+  // (A narrower geometry at small B -- 16 one-wave workgroups at B = 1 -- staged the lines 16 times and met in
+  // per-group tickets: the value+gradient envelope took 16.6 us against 14.1 us, profiles/r04/b1.)
   int sw = std::max(1, std::min(8, S));
   static const char* env = std::getenv("DKG_ENV_SW");  // A/B measurements: waves per workgroup
   if (env && std::atoi(env) >= 1) sw = std::max(1, std::min(std::atoi(env), sw));
-  if (narrow && DKG_ENV_NARROW)
-    while (sw > 1 && (long long)B * ((S + sw - 1) / sw) < ENV_MIN_WGS) sw = (sw + 1) / 2;
   *waves_per_wg = sw;
   *split = (S + sw - 1) / sw;
 }
@@ -878,8 +867,7 @@ hipError_t launch_stage(const Plan& h, const Plan* dev, const double* xnew, int 
   }
   // (several targets: ntgt items per candidate, the workgroups of a candidate's items side by side)
   EnvLaunch a{&h, dev, B, kg, pairs, dim3(xcd_group_size(B, h.split * h.ntgt)), dim3(h.sw * WAVE),
-              envelope_lds_bytes(h.m, h.N, h.sw, h.S, h.stream != 0, false, !DKG_ICP), s, h.debug_stamp, nullptr,
-              nullptr};
+              envelope_lds_bytes(h.m, h.N, h.sw, h.S, h.stream != 0), s, h.debug_stamp, nullptr, nullptr};
   return launch_env<false>(h, a);
 }
 

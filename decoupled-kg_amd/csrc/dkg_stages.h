@@ -6,10 +6,6 @@
 
 #include "dkg_device.h"
 
-#ifndef DKG_DUP_MARK  // A/B only: 0 drops the coincidence marks of the staged covariance (Plan::dup)
-#define DKG_DUP_MARK 1
-#endif
-
 namespace dkg {
 
 // Element-type plumbing of the two contractions (T = double: the reference's
@@ -522,7 +518,7 @@ __device__ __forceinline__ void posterior_cov_body(const Plan* __restrict__ P, c
       kv[rr] = os * kernel_term_nc(kind, r2, EPI_FIRST ? tab : psi_tab());
       // rounded here, never fused into the epilogue's subtraction: posterior_cov_big_kernel gives the same bits
       asm("" : "+v"(kv[rr]));
-      if (DKG_DUP_MARK) hm[rr] = ballot(r2 == 0.0);
+      hm[rr] = ballot(r2 == 0.0);
     }
   }
   if constexpr (HO) {
@@ -746,10 +742,10 @@ __device__ __forceinline__ double2 gload_d2(const double* p) {
 // are in flight, so the epilogue only stores (in registers they would stay live across the contraction).
 // Returns the r^2 == 0 bits (Plan::dup), one per element.  scaled_r2_dm's and kernel_term_nc's arithmetic
 // (compiled without FP contraction, dkg_common.h), so the terms are posterior_cov_body's bits.
-template <int DM, class T, class Sink>
+template <int DM, class T>
 __device__ __forceinline__ uint32_t big_block_terms(const Plan* __restrict__ P, const dkg_output& o,
                                                     const double* __restrict__ xnew, int B, int tr, int tc, int lane,
-                                                    Sink&& sink) {
+                                                    double* __restrict__ kvs) {
   const int N = P->N, d = P->d;
   const double os = o.outputscale;
   const int kind = o.kernel;
@@ -788,7 +784,7 @@ __device__ __forceinline__ uint32_t big_block_terms(const Plan* __restrict__ P, 
           }
           const double kv = os * kernel_term_nc<KIND>(r2, tab);  // rounded (stored), as posterior_cov_body
           const int e = (g * 2 + h) * 4 + r;
-          sink(e, kv);
+          kvs[e * 64 + lane] = kv;
           zero_r2 |= (r2 == 0.0 ? 1u : 0u) << e;
         }
       }
@@ -802,14 +798,6 @@ __device__ __forceinline__ uint32_t big_block_terms(const Plan* __restrict__ P, 
   return zero_r2;
 }
 
-template <int DM, class T>
-__device__ __forceinline__ uint32_t big_block_terms(const Plan* __restrict__ P, const dkg_output& o,
-                                                    const double* __restrict__ xnew, int B, int tr, int tc, int lane,
-                                                    double* __restrict__ kvs) {
-  return big_block_terms<DM, T>(P, o, xnew, B, tr, tc, lane,
-                                [&](int e, double kv) __attribute__((always_inline)) { kvs[e * 64 + lane] = kv; });
-}
-
 constexpr int PB_WAVES = 4;
 constexpr int PB_RT = 4;  // candidate tiles per block
 constexpr int PB_CT = 4;  // line tiles per block
@@ -817,18 +805,13 @@ constexpr int PB_CT = 4;  // line tiles per block
 #define DKG_PB_WC 2
 #endif
 constexpr int PB_WC = DKG_PB_WC;  // words (two k-blocks each) per staged chunk (2 or 4); even, so chains restart in step
-// the kernel terms in registers (16 per lane) instead of parked in LDS: the LDS then holds the stage buffers only
-#ifndef DKG_PB_KVREG
-#define DKG_PB_KVREG 0
-#endif
-constexpr bool PB_KVREG = DKG_PB_KVREG != 0;
 constexpr int PB_STAGE = (PB_RT + PB_CT) * PB_WC * 64;  // 16-byte words per stage buffer
 #ifndef DKG_PB_NSTG
 #define DKG_PB_NSTG 2
 #endif
 constexpr int PB_NSTG = DKG_PB_NSTG;                               // stage buffers: chunks in flight + the one computed
 // the stage buffers, then the kernel terms (16 per lane per wave): 64 KiB, two workgroups per CU
-constexpr size_t PB_LDS = PB_NSTG * (size_t)PB_STAGE * 16 + (PB_KVREG ? 0 : (size_t)PB_WAVES * 16 * 64 * 8);
+constexpr size_t PB_LDS = PB_NSTG * (size_t)PB_STAGE * 16 + (size_t)PB_WAVES * 16 * 64 * 8;
 
 template <int DM>
 __global__ __launch_bounds__(PB_WAVES * WAVE) __attribute__((amdgpu_waves_per_eu(2))) void posterior_cov_big_kernel(
@@ -901,17 +884,7 @@ __global__ __launch_bounds__(PB_WAVES * WAVE) __attribute__((amdgpu_waves_per_eu
   // r^2 == 0 (Plan::dup) as one bit per element.
   const double os = o.outputscale;
   double* kvs = reinterpret_cast<double*>(stg + (size_t)PB_NSTG * PB_STAGE) + (size_t)wave * 16 * 64;
-  double kvr[PB_KVREG ? 16 : 1];
-  uint32_t zero_r2;
-  if constexpr (PB_KVREG) {
-    zero_r2 = big_block_terms<DM, double>(P, o, xnew, B, ti0 + 2 * rp, tk0 + 2 * cp, lane,
-                                          [&](int e, double kv) __attribute__((always_inline)) {
-                                            asm volatile("" : "+v"(kv));  // rounded here (never fused later)
-                                            kvr[e] = kv;
-                                          });
-  } else {
-    zero_r2 = big_block_terms<DM, double>(P, o, xnew, B, ti0 + 2 * rp, tk0 + 2 * cp, lane, kvs);
-  }
+  const uint32_t zero_r2 = big_block_terms<DM, double>(P, o, xnew, B, ti0 + 2 * rp, tk0 + 2 * cp, lane, kvs);
   KST(st, 2);
   for (int c = 0; c < nc; ++c) {
     // chunk c landed (this wave's pieces), then every wave's: the later chunks' DMAs stay in flight
@@ -1049,9 +1022,8 @@ __global__ __launch_bounds__(PB_WAVES * WAVE) __attribute__((amdgpu_waves_per_eu
         const int b = 16 * (ti0 + 2 * rp + h) + mfma_drow<double>(le, r);
         const int e = (g * 2 + h) * 4 + r;
         if (b < B && k < N) {
-          P->cov_all[(size_t)b * P->cov_stride + (size_t)k * rec + oi] =
-              (PB_KVREG ? kvr[PB_KVREG ? e : 0] : kvs[e * 64 + le]) - tot[h][g][r];
-          if (DKG_DUP_MARK && ((zero_r2 >> e) & 1)) atomicMin(&P->dup[b], k);  // Plan::dup
+          P->cov_all[(size_t)b * P->cov_stride + (size_t)k * rec + oi] = kvs[e * 64 + le] - tot[h][g][r];
+          if ((zero_r2 >> e) & 1) atomicMin(&P->dup[b], k);  // Plan::dup
         }
       }
   }
@@ -1255,7 +1227,7 @@ __global__ __launch_bounds__(PR_WAVES * WAVE) __attribute__((amdgpu_waves_per_eu
       if (b < B && k < N) {
         const double kt = kvs[(h * 4 + r) * 64 + le];
         P->cov_all[(size_t)b * P->cov_stride + (size_t)k * rec + oi] = kt - sum;
-        if (DKG_DUP_MARK && ((zero_r2 >> ((h - hlo) * 4 + r)) & 1)) atomicMin(&P->dup[b], k);  // Plan::dup
+        if ((zero_r2 >> ((h - hlo) * 4 + r)) & 1) atomicMin(&P->dup[b], k);  // Plan::dup
       }
     }
   }
@@ -1451,7 +1423,7 @@ __global__ __launch_bounds__(PR_WAVES * WAVE) __attribute__((amdgpu_waves_per_eu
       const int rl = 16 * h + mfma_drow<double>(lane, r);
       const double sum = tot[h][r] + xch[(h * 4 + r) * 64 + lane];  // half 0 + half 1 (commutes)
       rtile[((size_t)rl * 32 + 16 * lt + (lane & 15)) * 2 + oi] = kvs[(h * 4 + r) * 64 + lane] - sum;
-      if (DKG_DUP_MARK && ((zero_r2 >> ((h - hlo) * 4 + r)) & 1)) {
+      if ((zero_r2 >> ((h - hlo) * 4 + r)) & 1) {
         const int b = 16 * (ti0 + h) + mfma_drow<double>(lane, r);
         if (b < B && kcol < N) atomicMin(&P->dup[b], kcol);  // Plan::dup
       }
@@ -1677,7 +1649,7 @@ __global__ __launch_bounds__(PB_WAVES * WAVE) __attribute__((amdgpu_waves_per_eu
       const int b = 16 * ti + mfma_drow<double>(le, r);
       if (b < B && k < N) {
         P->cov_all[(size_t)b * P->cov_stride + (size_t)k * rec + oi] = kv[g][r] - tot[r];
-        if (DKG_DUP_MARK && ((zero_r2 >> (g * 4 + r)) & 1)) atomicMin(&P->dup[b], k);  // Plan::dup
+        if ((zero_r2 >> (g * 4 + r)) & 1) atomicMin(&P->dup[b], k);  // Plan::dup
       }
     }
   }
@@ -1837,7 +1809,7 @@ __global__ __launch_bounds__(PB_WAVES * WAVE) __attribute__((amdgpu_waves_per_eu
         const int e = (g * 2 + h) * 4 + r;
         if (b < B && k < N) {
           P->cov_all[(size_t)b * P->cov_stride + (size_t)k * rec + oi] = kvs[e * 64 + le] - sum[h][g][r];
-          if (DKG_DUP_MARK && ((zero_r2 >> e) & 1)) atomicMin(&P->dup[b], k);  // Plan::dup
+          if ((zero_r2 >> e) & 1) atomicMin(&P->dup[b], k);  // Plan::dup
         }
       }
   }
@@ -1868,13 +1840,10 @@ __global__ __launch_bounds__(PB_WAVES * WAVE) __attribute__((amdgpu_waves_per_eu
 // fetches).  Blocks of 32 columns: the longest (k = n) takes 128 words x 4 MFMAs per wave at n = 1024, so the
 // triangle's longest blocks are not the whole stage; they are dispatched first, and the candidate blocks of one
 // column block and output sit side by side on one XCD (xcd_group), sharing its R panel.
-#ifndef DKG_XB_WAVES
-#define DKG_XB_WAVES 4
-#endif
-constexpr int XB_WAVES = DKG_XB_WAVES;  // 4; 2 (32 x 32 blocks, twice the workgroups) was slower: stress cross
-                                        // 43.7 -> 48.6 us, headline x 10 21.2 -> 24.4 us
+constexpr int XB_WAVES = 4;  // 2 (32 x 32 blocks, twice the workgroups) was slower: stress cross
+                             // 43.7 -> 48.6 us, headline x 10 21.2 -> 24.4 us
 constexpr int XB_TT = 2;  // column tiles of Q (row tiles of R^T) per block
-constexpr int XB_RT = XB_WAVES == 2 ? 2 : 4;  // candidate tiles per block
+constexpr int XB_RT = 4;  // candidate tiles per block
 constexpr int XB_WC = 4;  // words per staged chunk (one barrier per 16 MFMAs per wave)
 constexpr int XB_STAGE = (XB_TT + XB_RT) * XB_WC * 64;  // 16-byte words per stage buffer
 #ifndef DKG_XB_NSTG
@@ -1909,7 +1878,7 @@ __device__ __forceinline__ void cross_big_body(const Plan* __restrict__ P, int B
   const int W = 2 * min(tj0 + XB_TT, T);  // words the block reads: its last live column tile's k range
   const int nc = (W + XB_WC - 1) / XB_WC;
   constexpr int XB_PIECES = (XB_TT + XB_RT) * XB_WC / XB_WAVES;
-  static_assert((XB_TT + XB_RT) * XB_WC % XB_WAVES == 0 && (XB_PIECES == 6 || XB_PIECES == 8), "DMA pieces per wave");
+  static_assert((XB_TT + XB_RT) * XB_WC % XB_WAVES == 0 && XB_PIECES == 6, "six DMA pieces per wave");
   auto stage = [&](int c) {
     const int j0 = c * XB_WC, nw = min(XB_WC, W - j0);
     double2* buf = stg + (size_t)(c % XB_NSTG) * XB_STAGE;
@@ -1947,6 +1916,8 @@ __device__ __forceinline__ void cross_big_body(const Plan* __restrict__ P, int B
   for (int c = 0; c < nc; ++c) {
     // chunk c landed: the chunks issued after it (at most XB_NSTG - 2, XB_PIECES pieces each) may stay in flight
     static_assert(XB_NSTG >= 2 && XB_NSTG <= 4, "vmcnt cases");
+    // (six pieces per chunk: the value is 0, 6 or, with four stage buffers, 12.  Cases 16 and 8 are dead; they are
+    // kept because dropping them changed the kernel's code)
     switch (min(nc - 1 - c, XB_NSTG - 2) * XB_PIECES) {  // wave-uniform
       case 16: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
       case 12: asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); break;

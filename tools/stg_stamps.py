@@ -1,7 +1,8 @@
-"""Wait vs compute of the staged streaming passes (library built with EXTRA=-DDKG_STG_STAMPS).
+"""Phases of the staged streaming forward (library built with EXTRA=-DDKG_STG_STAMPS).
 
 Run on the GPU box:  python tools/stg_stamps.py [workload]   (envelope workgroups: slot 3 = passes start,
-4 = wave 0's cycles waiting at the chunk barriers, 5 = passes end, 6 = workgroup end)
+4 = pass 0 (the sample hull) done, 5 = the staged pass done, 6 = workgroup end; the hull sizes hold the list
+lengths in this build)
 """
 import ctypes
 import os
@@ -32,20 +33,13 @@ _lib.check(_lib.load().dkg_debug_read_kstamps(buf, n), "kstamps")
 st = np.frombuffer(buf, dtype=np.uint64).reshape(3, 1024, 8).astype(np.int64)[2]
 st = st[st[:, 0] > 0]
 passes = st[:, 5] - st[:, 3]
-wait = st[:, 4]
 tail = st[:, 6] - st[:, 5]
 q = lambda v: f"median {np.median(v):8.0f} p90 {np.percentile(v, 90):8.0f} max {v.max():8.0f}"
 print(f"{len(st)} envelope WGs")
 print("passes      ", q(passes))
-print("  waiting   ", q(wait))
-print("  computing ", q(passes - wait))
+print("pass 0 (sample hull)", q(st[:, 4] - st[:, 3]))
+print("staged pass         ", q(st[:, 5] - st[:, 4]))
 print("tail (refine/walk/sum)", q(tail))
-if os.environ.get("DKG_STG_SAMPLE", "1") != "0":
-    # sample-hull build: slot 4 = pass 0 (sample hull) done, slot 5 = the staged pass done; hull sizes hold
-    # the list lengths
-    p0 = st[:, 4] - st[:, 3]
-    print("pass 0 (sample hull)", q(p0))
-    print("staged pass         ", q(st[:, 5] - st[:, 4]))
-    _, _, cnt = plan.forward_stats(Xd)
-    c = cnt.flatten().cpu().numpy().astype(np.int64)
-    print("list length          ", q(c), "over 512:", int((c > 512).sum()), "of", c.size)
+_, _, cnt = plan.forward_stats(Xd)
+c = cnt.flatten().cpu().numpy().astype(np.int64)
+print("list length          ", q(c), "over 512:", int((c > 512).sum()), "of", c.size)
