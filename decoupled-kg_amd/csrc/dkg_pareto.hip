@@ -1,0 +1,621 @@
+// Posterior-mean Pareto front on the device (gfx950): a mean-only posterior kernel and NSGA-II (Deb et al. 2002)
+// whose generations stay on the device.  The reference samples the front of the surrogate's posterior mean with
+// pygmo.nsga2 at every BO iteration (modules/pareto/sample.py:16-48, bo_loop.py:294-332, 480-520), its fitness
+// BoTorchModel.batch_fitness (sample.py:138-144) or GPTestProblem.evaluate_true (gp_testproblem.py:76-97).
+//
+//   posterior_mean_kernel   mean[p][i] = y_mean_i + y_std_i (c_i + K(x_p, X_i) alpha_i).  One workgroup per
+//                           (16 points, output): X_i (pre-scaled by 1 / lengthscale, as the cross stage stages it)
+//                           and alpha_i in LDS, one wave per point, lane l the training points l, l + 64, ... as one
+//                           fma chain, then wave_sum's fixed-order reduction.  No atomics: a point's bits depend on
+//                           the point alone, not on P or on its row.
+//   pareto_rank_kernel      one workgroup: dominator counts, the front peel (fast non-dominated sort), crowding
+//                           distances by rank-in-front scans (no sort: a member's neighbours in (f_j, index) order
+//                           are the largest key below and the smallest key above its own), and the survivor order
+//                           by counting the keys (rank, -crowding, index) below a point's own.  Every loop is
+//                           bounded by Q; phases meet at __syncthreads.
+//   pareto_variation_kernel binary tournament, bounded simulated binary crossover (Deb & Agrawal 1995) and bounded
+//                           polynomial mutation (Deb et al. 2002), one thread per (pair of children, coordinate),
+//                           every random number read from the caller's uniforms (layout: include/dkg.h).
+//   pareto_init / normalise / gather: the glue of dkg_pareto_nsga2.
+// The three stages' arithmetic is compiled without FP contraction where a host restatement must give the same bits
+// (crowding) or nearly so (variation).
+#include <cstdarg>
+#include <cstdio>
+
+#include "dkg_stages.h"
+
+namespace dkg {
+
+constexpr int PM_WAVES = 4;   // waves per workgroup of posterior_mean_kernel
+constexpr int PM_POINTS = 16; // points per workgroup (4 per wave, one after the other)
+
+struct MeanArgs {
+  Outputs outs;
+  int m, d, P;
+  const double* x;  // [P][d] model inputs
+  double* mean;     // [P][m]
+};
+
+__host__ __device__ inline size_t mean_lds_bytes(int n, int d) { return (size_t)n * (d + 1) * sizeof(double); }
+
+template <int DM>
+__global__ __launch_bounds__(PM_WAVES* WAVE) void posterior_mean_kernel(MeanArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double pm_smem[];
+  const dkg_output& o = a.outs.o[blockIdx.y];
+  const int n = o.n, d = a.d;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double* xs = pm_smem;                // [n][d] training inputs / lengthscale
+  double* als = pm_smem + (size_t)n * d;  // [n]
+  for (int e = tid; e < n * d; e += PM_WAVES * WAVE) xs[e] = o.train_x[e] * o.inv_lengthscale[e % d];
+  for (int e = tid; e < n; e += PM_WAVES * WAVE) als[e] = o.alpha[e];
+  __syncthreads();
+  const double os = o.outputscale;
+  const int iters = (n + WAVE - 1) / WAVE;  // wave-uniform trip count
+  const int p0 = blockIdx.x * PM_POINTS;
+  for (int q = wave; q < PM_POINTS; q += PM_WAVES) {
+    const int p = p0 + q;
+    if (p >= a.P) break;  // wave-uniform
+    double xr[DM];
+#pragma unroll
+    for (int k = 0; k < DM; ++k) {
+      const int kk = min(k, d - 1);
+      xr[k] = a.x[(size_t)p * d + kk] * o.inv_lengthscale[kk];
+    }
+    double acc = 0.0;
+    auto chain = [&](auto kind_c) {
+      constexpr int KIND = decltype(kind_c)::value;
+      const const_dptr tab = psi_tab();
+      for (int it = 0; it < iters; ++it) {
+        const int j = lane + it * WAVE;
+        const int jc = min(j, n - 1);
+        const double kv = cross_kernel_term<DM, KIND>(xr, xs + (size_t)jc * d, d, os, tab);
+        acc = fma((j < n) ? kv : 0.0, als[jc], acc);
+      }
+    };
+    switch (o.kernel) {
+      case DKG_MATERN12: chain(std::integral_constant<int, DKG_MATERN12>{}); break;
+      case DKG_MATERN32: chain(std::integral_constant<int, DKG_MATERN32>{}); break;
+      case DKG_RBF: chain(std::integral_constant<int, DKG_RBF>{}); break;
+      default: chain(std::integral_constant<int, DKG_MATERN52>{}); break;
+    }
+    const double s = wave_sum(acc);
+    if (lane == 0) a.mean[(size_t)p * a.m + blockIdx.y] = fma(o.y_std, o.mean_constant + s, o.y_mean);
+  }
+}
+
+static hipError_t launch_mean(const MeanArgs& a, hipStream_t s) {
+  int nmax = 1;
+  for (int i = 0; i < a.m; ++i) nmax = std::max(nmax, (int)a.outs.o[i].n);
+  const size_t lds = mean_lds_bytes(nmax, a.d);
+  const dim3 grid((a.P + PM_POINTS - 1) / PM_POINTS, a.m), block(PM_WAVES * WAVE);
+  auto go = [&](auto kern) {
+    raise_lds_limit(reinterpret_cast<const void*>(kern), lds);
+    hipLaunchKernelGGL(kern, grid, block, lds, s, a);
+  };
+  switch (dim_bucket(a.d)) {
+    case 2: go(posterior_mean_kernel<2>); break;
+    case 4: go(posterior_mean_kernel<4>); break;
+    case 8: go(posterior_mean_kernel<8>); break;
+    default: go(posterior_mean_kernel<16>); break;
+  }
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Ranks, crowding distances and survivor order of Q <= 2048 points in one workgroup; thread t owns the points
+// t and t + blockDim.x.  LDS: F [Q][m], then rk [Q] and the current front's member list [Q].
+constexpr int PR_MAXQ = 2048;
+constexpr int PR_PPT = 2;  // points per thread
+
+__host__ __device__ inline size_t rank_lds_bytes(int Q, int m) {
+  return (size_t)Q * m * sizeof(double) + 2 * (size_t)Q * sizeof(int) + 16;
+}
+
+// Row i of f [Q][m] in MB >= m registers; the entries j >= m repeat entry m - 1 (clamped loads, no branches), which
+// changes no dominance test.
+template <int MB>
+__device__ __forceinline__ void load_row(const double* f, int i, int m, double (&r)[MB]) {
+#pragma unroll
+  for (int j = 0; j < MB; ++j) r[j] = f[(size_t)i * m + min(j, m - 1)];
+}
+
+// a dominates b: a >= b in every objective and a > b in at least one (all maximised)
+template <int MB>
+__device__ __forceinline__ bool dominates(const double (&fa)[MB], const double (&fb)[MB]) {
+  bool ge = true, gt = false;
+#pragma unroll
+  for (int j = 0; j < MB; ++j) {
+    ge = ge && (fa[j] >= fb[j]);
+    gt = gt || (fa[j] > fb[j]);
+  }
+  return ge && gt;
+}
+
+// MB: the objectives' register bucket (2, 4 or 8 >= m).  The scans over the Q points are branch-free and unrolled
+// so that their LDS reads are in flight together: one workgroup's scans are bound by LDS latency, not arithmetic.
+template <int MB>
+__global__ __launch_bounds__(1024) void pareto_rank_kernel(const double* __restrict__ F, int Q, int m, int keep,
+                                                           int* __restrict__ rank, double* __restrict__ crowd,
+                                                           int* __restrict__ order) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) double pr_smem[];
+  double* f = pr_smem;                                   // [Q][m]; after the crowding phase [Q] crowding distances
+  int* rk = reinterpret_cast<int*>(pr_smem + (size_t)Q * m);  // [Q]: -2 not yet ranked, else the front
+  int* list = rk + Q;                                    // [Q]: members of the front being peeled
+  int* cnts = list + Q;                                  // [0] members of the front, [1] points ranked so far
+  const int tid = threadIdx.x, nt = blockDim.x;
+  for (int e = tid; e < Q * m; e += nt) f[e] = F[e];
+  for (int e = tid; e < Q; e += nt) {
+    rk[e] = -2;
+    order[e] = -1;
+  }
+  if (tid < 2) cnts[tid] = 0;
+  __syncthreads();
+  // dominator counts of the thread's points
+  int cnt[PR_PPT];
+  double own[PR_PPT][MB];  // the thread's rows (a slot past Q holds row Q - 1 and is never used)
+#pragma unroll
+  for (int s = 0; s < PR_PPT; ++s) {
+    load_row<MB>(f, min(tid + s * nt, Q - 1), m, own[s]);
+    cnt[s] = 0;
+  }
+#pragma unroll 4
+  for (int k = 0; k < Q; ++k) {
+    double fk[MB];
+    load_row<MB>(f, k, m, fk);
+#pragma unroll
+    for (int s = 0; s < PR_PPT; ++s) cnt[s] += dominates<MB>(fk, own[s]) ? 1 : 0;
+  }
+  // peel: front r = the unranked points no unranked point dominates; at most Q fronts
+  for (int r = 0; r < Q; ++r) {
+#pragma unroll
+    for (int s = 0; s < PR_PPT; ++s) {
+      const int i = tid + s * nt;
+      if (i < Q && rk[i] == -2 && cnt[s] == 0) list[atomicAdd(&cnts[0], 1)] = i;  // any order: only counted over
+    }
+    __syncthreads();
+    const int nf = cnts[0];
+    const int done = cnts[1] + nf;
+#pragma unroll
+    for (int s = 0; s < PR_PPT; ++s) {
+      const int i = tid + s * nt;
+      if (i < Q && rk[i] == -2) {
+        if (cnt[s] == 0) {
+          cnt[s] = -1;  // ranked below, after every thread has read this round's rk
+        } else {
+          int c = 0;
+#pragma unroll 4
+          for (int q = 0; q < nf; ++q) {
+            double fk[MB];
+            load_row<MB>(f, list[q], m, fk);
+            c += dominates<MB>(fk, own[s]) ? 1 : 0;
+          }
+          cnt[s] -= c;
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < PR_PPT; ++s) {
+      const int i = tid + s * nt;
+      if (i < Q && cnt[s] == -1) {
+        rk[i] = r;
+        cnt[s] = -3;
+      }
+    }
+    if (tid == 0) {
+      cnts[0] = 0;
+      cnts[1] = done;
+    }
+    __syncthreads();
+    if (done >= keep || nf == 0) break;  // uniform: read from LDS before the barrier above
+  }
+  // crowding within each ranked front, objectives in order; one subtraction, division and addition per step
+  double cd[PR_PPT];
+#pragma unroll
+  for (int s = 0; s < PR_PPT; ++s) {
+    const int i = tid + s * nt;
+    cd[s] = 0.0;
+    if (i >= Q || rk[i] < 0) continue;
+    const int ri = rk[i];
+    for (int j = 0; j < m; ++j) {
+      const double fi = f[(size_t)i * m + j];
+      double fmin = fi, fmax = fi, prev = 0.0, next = 0.0;
+      bool hp = false, hn = false;
+#pragma unroll 4
+      for (int k = 0; k < Q; ++k) {
+        const bool in = rk[k] == ri;
+        const double fk = f[(size_t)k * m + j];
+        fmin = (in && fk < fmin) ? fk : fmin;
+        fmax = (in && fk > fmax) ? fk : fmax;
+        // before / after i in (f_j, index) order: the predecessor is the largest f before, the successor the
+        // smallest f after
+        const bool before = in && (fk < fi || (fk == fi && k < i));
+        const bool after = in && (fk > fi || (fk == fi && k > i));
+        prev = (before && (!hp || fk > prev)) ? fk : prev;
+        next = (after && (!hn || fk < next)) ? fk : next;
+        hp = hp || before;
+        hn = hn || after;
+      }
+      if (!hp || !hn) {
+        cd[s] = cd[s] + __builtin_inf();
+      } else {
+        const double range = fmax - fmin;
+        const double num = next - prev;
+        cd[s] = cd[s] + (range > 0.0 ? num / range : 0.0);
+      }
+    }
+  }
+  __syncthreads();  // every read of f as objectives is done: it now holds the crowding distances
+#pragma unroll
+  for (int s = 0; s < PR_PPT; ++s) {
+    const int i = tid + s * nt;
+    if (i < Q) {
+      f[i] = cd[s];
+      crowd[i] = cd[s];
+      rank[i] = rk[i] < 0 ? -1 : rk[i];
+    }
+  }
+  __syncthreads();
+  // survivor order: a ranked point's position is the number of ranked points whose key (rank, -crowding, index)
+  // is below its own; positions are < Q whatever the values
+#pragma unroll
+  for (int s = 0; s < PR_PPT; ++s) {
+    const int i = tid + s * nt;
+    if (i >= Q || rk[i] < 0) continue;
+    const int ri = rk[i];
+    const double ci = f[i];
+    int pos = 0;
+#pragma unroll 4
+    for (int k = 0; k < Q; ++k) {
+      const int rkk = rk[k];
+      const double ck = f[k];
+      const bool before = rkk >= 0 && (rkk < ri || (rkk == ri && (ck > ci || (ck == ci && k < i))));
+      pos += before ? 1 : 0;
+    }
+    order[pos] = i;
+  }
+}
+
+static hipError_t launch_rank(const double* F, int Q, int m, int keep, int* rank, double* crowd, int* order,
+                              hipStream_t s) {
+  const size_t lds = rank_lds_bytes(Q, m);
+  const int nt = std::min(1024, std::max(64, (Q + 63) / 64 * 64));
+  auto go = [&](auto kern) {
+    raise_lds_limit(reinterpret_cast<const void*>(kern), lds);
+    hipLaunchKernelGGL(kern, dim3(1), dim3(nt), lds, s, F, Q, m, keep, rank, crowd, order);
+  };
+  if (m <= 2) go(pareto_rank_kernel<2>);
+  else if (m <= 4) go(pareto_rank_kernel<4>);
+  else go(pareto_rank_kernel<8>);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Variation.  Draw layout (include/dkg.h): u[2 w], u[2 w + 1] the tournament of winner w; then per pair k < P / 2
+// its crossover gate; then per (pair, coordinate) three numbers (cross this coordinate, the spread, swap); then per
+// (child, coordinate) two (mutate, the perturbation).
+struct VarArgs {
+  const double* X;      // [P][d]
+  const int* rank;      // [P]
+  const double* crowd;  // [P]
+  const double *lb, *ub;
+  const double* u;
+  double* child;  // [P][d]
+  int P, d;
+  double cr, eta_c, pm, eta_m;
+};
+
+__device__ __forceinline__ int tournament(const VarArgs& a, int w) {
+  const int P = a.P;
+  int i0 = (int)(a.u[2 * w] * P), i1 = (int)(a.u[2 * w + 1] * P);
+  i0 = max(0, min(i0, P - 1));
+  i1 = max(0, min(i1, P - 1));
+  const int r0 = a.rank[i0], r1 = a.rank[i1];
+  const bool second = r1 < r0 || (r1 == r0 && a.crowd[i1] > a.crowd[i0]);
+  return second ? i1 : i0;
+}
+
+__device__ __forceinline__ double clip(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+__device__ __forceinline__ double sbx_betaq(double u, double beta, double eta) {
+#pragma clang fp contract(off)
+  const double alpha = 2.0 - pow(beta, -(eta + 1.0));
+  const double e = 1.0 / (eta + 1.0);
+  return (u <= 1.0 / alpha) ? pow(u * alpha, e) : pow(1.0 / (2.0 - u * alpha), e);
+}
+
+__device__ __forceinline__ double poly_mutate(double y, double lo, double hi, double u, double eta) {
+#pragma clang fp contract(off)
+  const double span = hi - lo;
+  if (!(span > 0.0)) return y;
+  const double d1 = (y - lo) / span, d2 = (hi - y) / span;
+  const double mp = 1.0 / (eta + 1.0);
+  double dq;
+  if (u < 0.5) {
+    const double xy = 1.0 - d1;
+    const double val = 2.0 * u + (1.0 - 2.0 * u) * pow(xy, eta + 1.0);
+    dq = pow(val, mp) - 1.0;
+  } else {
+    const double xy = 1.0 - d2;
+    const double val = 2.0 * (1.0 - u) + 2.0 * (u - 0.5) * pow(xy, eta + 1.0);
+    dq = 1.0 - pow(val, mp);
+  }
+  return clip(y + dq * span, lo, hi);
+}
+
+__global__ __launch_bounds__(256) void pareto_variation_kernel(VarArgs a) {
+#pragma clang fp contract(off)
+  const int P = a.P, d = a.d, H = P / 2;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= H * d) return;
+  const int k = t / d, c = t - k * d;
+  const int w0 = tournament(a, 2 * k), w1 = tournament(a, 2 * k + 1);
+  const double lo = a.lb[c], hi = a.ub[c];
+  double c0 = a.X[(size_t)w0 * d + c], c1 = a.X[(size_t)w1 * d + c];
+  const double* ug = a.u + 2 * (size_t)P;
+  const double* ux = ug + H + 3 * ((size_t)k * d + c);
+  if (ug[k] < a.cr && ux[0] < 0.5) {
+    const double y1 = c0 < c1 ? c0 : c1, y2 = c0 < c1 ? c1 : c0;
+    const double dy = y2 - y1;
+    if (dy > 1e-14) {
+      const double bq1 = sbx_betaq(ux[1], 1.0 + 2.0 * (y1 - lo) / dy, a.eta_c);
+      const double bq2 = sbx_betaq(ux[1], 1.0 + 2.0 * (hi - y2) / dy, a.eta_c);
+      const double n1 = clip(0.5 * ((y1 + y2) - bq1 * dy), lo, hi);
+      const double n2 = clip(0.5 * ((y1 + y2) + bq2 * dy), lo, hi);
+      const bool swap = ux[2] < 0.5;
+      c0 = swap ? n2 : n1;
+      c1 = swap ? n1 : n2;
+    }
+  }
+  const double* um = ug + H + 3 * (size_t)H * d;
+  const double* m0 = um + 2 * ((size_t)(2 * k) * d + c);
+  const double* m1 = um + 2 * ((size_t)(2 * k + 1) * d + c);
+  if (m0[0] < a.pm) c0 = poly_mutate(c0, lo, hi, m0[1], a.eta_m);
+  if (m1[0] < a.pm) c1 = poly_mutate(c1, lo, hi, m1[1], a.eta_m);
+  a.child[(size_t)(2 * k) * d + c] = clip(c0, lo, hi);
+  a.child[(size_t)(2 * k + 1) * d + c] = clip(c1, lo, hi);
+}
+
+static hipError_t launch_variation(const VarArgs& a, hipStream_t s) {
+  const int total = a.P / 2 * a.d;
+  hipLaunchKernelGGL(pareto_variation_kernel, dim3((total + 255) / 256), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// x[p][k] = lb[k] + u[p][k] (ub[k] - lb[k]), clipped into the bounds
+__global__ __launch_bounds__(256) void pareto_init_kernel(const double* __restrict__ u, const double* __restrict__ lb,
+                                                          const double* __restrict__ ub, int total, int d,
+                                                          double* __restrict__ x) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const int k = t % d;
+  x[t] = clip(lb[k] + u[t] * (ub[k] - lb[k]), lb[k], ub[k]);
+}
+
+// xn = (x - lb) / (ub - lb): botorch's normalize (sample.py:129-130, 142)
+__global__ __launch_bounds__(256) void pareto_normalise_kernel(const double* __restrict__ x,
+                                                               const double* __restrict__ lb,
+                                                               const double* __restrict__ ub, int total, int d,
+                                                               double* __restrict__ xn) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= total) return;
+  const int k = t % d;
+  xn[t] = (x[t] - lb[k]) / (ub[k] - lb[k]);
+}
+
+struct GatherArgs {
+  const int* order;     // [2 P], the first P entries the survivors
+  const double *X2, *F2, *crowd2;
+  const int* rank2;
+  double *X, *F, *crowd;
+  int* rank;
+  int P, d, m;
+};
+
+// survivor r = point order[r] of [parents; children]
+__global__ __launch_bounds__(256) void pareto_gather_kernel(GatherArgs a) {
+  const int w = a.d + a.m + 2;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= a.P * w) return;
+  const int r = t / w, c = t - r * w;
+  const int src = a.order[r];
+  if (src < 0 || src >= 2 * a.P) return;  // never for r < keep; keeps a bad order in bounds
+  if (c < a.d) a.X[(size_t)r * a.d + c] = a.X2[(size_t)src * a.d + c];
+  else if (c < a.d + a.m) a.F[(size_t)r * a.m + (c - a.d)] = a.F2[(size_t)src * a.m + (c - a.d)];
+  else if (c == a.d + a.m) a.rank[r] = a.rank2[src];
+  else a.crowd[r] = a.crowd2[src];
+}
+
+}  // namespace dkg
+
+using namespace dkg;
+
+namespace {
+
+int pfail(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  return report_error(code, buf);
+}
+
+int phip(hipError_t e, const char* what) {
+  return e == hipSuccess ? DKG_OK : pfail(DKG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+}
+
+size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+int check_model(const dkg_output* outs, int m, int d) {
+  if (!outs) return pfail(DKG_ERR_ARG, "NULL pointer");
+  if (m < 1) return pfail(DKG_ERR_ARG, "m=%d outputs", m);
+  if (m > DKG_MAX_OUTPUTS) return pfail(DKG_ERR_UNSUPPORTED, "m=%d outputs (supported <= %d)", m, DKG_MAX_OUTPUTS);
+  if (d < 1) return pfail(DKG_ERR_ARG, "d=%d", d);
+  if (d > DKG_MAX_DIM) return pfail(DKG_ERR_UNSUPPORTED, "d=%d (supported 1..%d)", d, DKG_MAX_DIM);
+  for (int i = 0; i < m; ++i) {
+    if (outs[i].n < 1) return pfail(DKG_ERR_ARG, "output %d: n=%d training points", i, outs[i].n);
+    if (outs[i].n > 1024) return pfail(DKG_ERR_UNSUPPORTED, "output %d: n=%d > 1024 training points", i, outs[i].n);
+    if (outs[i].kernel < DKG_MATERN12 || outs[i].kernel > DKG_RBF)
+      return pfail(DKG_ERR_ARG, "output %d: kernel id %d", i, outs[i].kernel);
+    if (!outs[i].inv_lengthscale || !outs[i].train_x || !outs[i].alpha)
+      return pfail(DKG_ERR_ARG, "output %d: NULL pointer", i);
+  }
+  return DKG_OK;
+}
+
+int check_population(int P) {
+  if (P < 8 || P % 4) return pfail(DKG_ERR_ARG, "population P=%d (a multiple of 4, at least 8)", P);
+  if (P > 1024) return pfail(DKG_ERR_UNSUPPORTED, "population P=%d (supported <= 1024)", P);
+  return DKG_OK;
+}
+
+int check_params(const dkg_nsga2_params* p) {
+  if (!p) return pfail(DKG_ERR_ARG, "NULL pointer");
+  if (!(p->cr >= 0.0 && p->cr <= 1.0) || !(p->m >= 0.0 && p->m <= 1.0) || !(p->eta_c >= 0.0) || !(p->eta_m >= 0.0))
+    return pfail(DKG_ERR_ARG, "nsga2 parameters cr=%g eta_c=%g m=%g eta_m=%g", p->cr, p->eta_c, p->m, p->eta_m);
+  return DKG_OK;
+}
+
+MeanArgs mean_args(const dkg_output* outs, int m, int d, const double* x, int P, double* mean) {
+  MeanArgs a{};
+  for (int i = 0; i < m; ++i) a.outs.o[i] = outs[i];
+  a.m = m;
+  a.d = d;
+  a.P = P;
+  a.x = x;
+  a.mean = mean;
+  return a;
+}
+
+// dkg_pareto_nsga2's workspace carve
+struct NsgaWs {
+  size_t x2, f2, xn, crowd2, rank2, order, total;
+};
+NsgaWs nsga_ws(int P, int d, int m) {
+  NsgaWs w{};
+  size_t off = 0;
+  w.x2 = off;
+  off = up256(off + 2 * (size_t)P * d * sizeof(double));
+  w.f2 = off;
+  off = up256(off + 2 * (size_t)P * m * sizeof(double));
+  w.xn = off;
+  off = up256(off + (size_t)P * d * sizeof(double));
+  w.crowd2 = off;
+  off = up256(off + 2 * (size_t)P * sizeof(double));
+  w.rank2 = off;
+  off = up256(off + 2 * (size_t)P * sizeof(int));
+  w.order = off;
+  off = up256(off + 2 * (size_t)P * sizeof(int));
+  w.total = off;
+  return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dkg_posterior_mean(const dkg_output* outs, int m, int d, const double* x, int P, double* mean, void* stream) {
+  int st = check_model(outs, m, d);
+  if (st) return st;
+  if (P < 0 || P > (1 << 24)) return pfail(DKG_ERR_ARG, "P=%d points", P);
+  if (P == 0) return DKG_OK;
+  if (!x || !mean) return pfail(DKG_ERR_ARG, "NULL pointer");
+  return phip(launch_mean(mean_args(outs, m, d, x, P, mean), (hipStream_t)stream), "posterior_mean_kernel");
+}
+
+int dkg_pareto_rank(const double* F, int Q, int m, int keep, int* rank, double* crowd, int* order, void* work,
+                    size_t work_bytes, void* stream) {
+  (void)work;
+  (void)work_bytes;
+  if (Q < 1 || m < 1 || keep < 1 || keep > Q) return pfail(DKG_ERR_ARG, "Q=%d m=%d keep=%d", Q, m, keep);
+  if (Q > PR_MAXQ) return pfail(DKG_ERR_UNSUPPORTED, "Q=%d points (supported <= %d)", Q, PR_MAXQ);
+  if (m > DKG_MAX_OUTPUTS) return pfail(DKG_ERR_UNSUPPORTED, "m=%d objectives (supported <= %d)", m, DKG_MAX_OUTPUTS);
+  if (!F || !rank || !crowd || !order) return pfail(DKG_ERR_ARG, "NULL pointer");
+  return phip(launch_rank(F, Q, m, keep, rank, crowd, order, (hipStream_t)stream), "pareto_rank_kernel");
+}
+
+size_t dkg_pareto_draws(int P, int d) {
+  if (P < 2 || P % 2 || d < 1) return 0;
+  const size_t H = P / 2;
+  return 2 * (size_t)P + H + 3 * H * d + 2 * (size_t)P * d;
+}
+
+int dkg_pareto_variation(const double* X, const int* rank, const double* crowd, int P, int d, const double* lb,
+                         const double* ub, const dkg_nsga2_params* prm, const double* uniforms, double* children,
+                         void* stream) {
+  int st = check_population(P);
+  if (st) return st;
+  if (d < 1) return pfail(DKG_ERR_ARG, "d=%d", d);
+  if (d > DKG_MAX_DIM) return pfail(DKG_ERR_UNSUPPORTED, "d=%d (supported 1..%d)", d, DKG_MAX_DIM);
+  if ((st = check_params(prm))) return st;
+  if (!X || !rank || !crowd || !lb || !ub || !uniforms || !children) return pfail(DKG_ERR_ARG, "NULL pointer");
+  VarArgs a{X, rank, crowd, lb, ub, uniforms, children, P, d, prm->cr, prm->eta_c, prm->m, prm->eta_m};
+  return phip(launch_variation(a, (hipStream_t)stream), "pareto_variation_kernel");
+}
+
+size_t dkg_pareto_workspace(int P, int d, int m) {
+  if (P < 8 || P % 4 || P > 1024 || d < 1 || d > DKG_MAX_DIM || m < 1 || m > DKG_MAX_OUTPUTS) return 0;
+  return nsga_ws(P, d, m).total;
+}
+
+int dkg_pareto_nsga2(const dkg_output* outs, int m, int d, const double* lb, const double* ub, int P, int gens,
+                     const dkg_nsga2_params* prm, const double* uniforms, double* X, double* F, int* rank,
+                     double* crowd, void* work, size_t work_bytes, void* stream) {
+  int st = check_model(outs, m, d);
+  if (st) return st;
+  if ((st = check_population(P))) return st;
+  if (gens < 0 || gens > (1 << 20)) return pfail(DKG_ERR_ARG, "gens=%d generations", gens);
+  if ((st = check_params(prm))) return st;
+  if (!lb || !ub || !uniforms || !X || !F || !rank || !crowd || !work) return pfail(DKG_ERR_ARG, "NULL pointer");
+  const NsgaWs w = nsga_ws(P, d, m);
+  if (work_bytes < w.total) return pfail(DKG_ERR_WORKSPACE, "workspace %zu bytes < required %zu", work_bytes, w.total);
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(work);
+  double* X2 = reinterpret_cast<double*>(ws + w.x2);
+  double* F2 = reinterpret_cast<double*>(ws + w.f2);
+  double* Xn = reinterpret_cast<double*>(ws + w.xn);
+  double* crowd2 = reinterpret_cast<double*>(ws + w.crowd2);
+  int* rank2 = reinterpret_cast<int*>(ws + w.rank2);
+  int* order = reinterpret_cast<int*>(ws + w.order);
+  const int Pd = P * d, gb = (Pd + 255) / 256;
+  const bool raw = prm->raw_inputs != 0;
+  // evaluate `pts` (device [P][d], in the bounds) into `out` [P][m]
+  auto evaluate = [&](const double* pts, double* out) -> int {
+    const double* xin = pts;
+    if (!raw) {
+      hipLaunchKernelGGL(pareto_normalise_kernel, dim3(gb), dim3(256), 0, s, pts, lb, ub, Pd, d, Xn);
+      int e = phip(hipGetLastError(), "pareto_normalise_kernel");
+      if (e) return e;
+      xin = Xn;
+    }
+    return phip(launch_mean(mean_args(outs, m, d, xin, P, out), s), "posterior_mean_kernel");
+  };
+  hipLaunchKernelGGL(pareto_init_kernel, dim3(gb), dim3(256), 0, s, uniforms, lb, ub, Pd, d, X);
+  if ((st = phip(hipGetLastError(), "pareto_init_kernel")) || (st = evaluate(X, F)) ||
+      (st = phip(launch_rank(F, P, m, P, rank, crowd, order, s), "pareto_rank_kernel")))
+    return st;
+  const size_t draws = dkg_pareto_draws(P, d);
+  GatherArgs g{order, X2, F2, crowd2, rank2, X, F, crowd, rank, P, d, m};
+  const int gt = P * (d + m + 2);
+  for (int gen = 0; gen < gens; ++gen) {
+    double* Xc = X2 + (size_t)Pd;
+    double* Fc = F2 + (size_t)P * m;
+    VarArgs a{X, rank, crowd, lb, ub, uniforms + Pd + (size_t)gen * draws, Xc, P, d, prm->cr, prm->eta_c, prm->m,
+              prm->eta_m};
+    if ((st = phip(hipMemcpyAsync(X2, X, (size_t)Pd * sizeof(double), hipMemcpyDeviceToDevice, s), "hipMemcpyAsync")) ||
+        (st = phip(hipMemcpyAsync(F2, F, (size_t)P * m * sizeof(double), hipMemcpyDeviceToDevice, s),
+                   "hipMemcpyAsync")) ||
+        (st = phip(launch_variation(a, s), "pareto_variation_kernel")) || (st = evaluate(Xc, Fc)) ||
+        (st = phip(launch_rank(F2, 2 * P, m, P, rank2, crowd2, order, s), "pareto_rank_kernel")))
+      return st;
+    hipLaunchKernelGGL(pareto_gather_kernel, dim3((gt + 255) / 256), dim3(256), 0, s, g);
+    if ((st = phip(hipGetLastError(), "pareto_gather_kernel"))) return st;
+  }
+  return DKG_OK;
+}
+
+}  // extern "C"

@@ -18,7 +18,15 @@ from .discretekg import (
 )
 from .errors import BotorchTensorDimensionError, DkgNativeError, UnsupportedError
 from .gp_state import DeviceGPState, reset_state_stats, set_incremental_state, state_stats
+from .metrics import (
+    calculate_reference_point,
+    estimate_best_possible_expected_performance_after_scalarisation,
+    estimate_expected_performance_after_scalarisation,
+    estimate_hypervolume,
+    estimate_hypervolume_from_posterior_mean,
+)
 from .model import ModelListGPState, SingleTaskGPState, from_botorch, from_state_dict
+from .pareto import nondominated_rank, posterior_mean, sample_points_on_pareto_front
 from .utils import is_power_of_2, make_torch_std_grid, sample_simplex
 
 __all__ = [
@@ -43,6 +51,14 @@ __all__ = [
     "SingleTaskGPState",
     "from_botorch",
     "from_state_dict",
+    "posterior_mean",
+    "nondominated_rank",
+    "sample_points_on_pareto_front",
+    "calculate_reference_point",
+    "estimate_best_possible_expected_performance_after_scalarisation",
+    "estimate_expected_performance_after_scalarisation",
+    "estimate_hypervolume",
+    "estimate_hypervolume_from_posterior_mean",
     "is_power_of_2",
     "make_torch_std_grid",
     "sample_simplex",

@@ -53,8 +53,28 @@ class DkgOutput(ctypes.Structure):
     ]
 
 
+class DkgNsga2Params(ctypes.Structure):
+    """``struct dkg_nsga2_params`` (include/dkg.h); the defaults are pygmo.nsga2's documented ones."""
+
+    _fields_ = [("cr", c_double), ("eta_c", c_double), ("m", c_double), ("eta_m", c_double),
+                ("raw_inputs", c_int32), ("reserved", c_int32)]
+
+    def __init__(self, cr=0.95, eta_c=10.0, m=0.01, eta_m=50.0, raw_inputs=0):
+        super().__init__(cr, eta_c, m, eta_m, int(raw_inputs), 0)
+
+
 # name -> (restype, argtypes); every symbol include/dkg.h declares.
 SIGNATURES = {
+    "dkg_posterior_mean": (c_int, [POINTER(DkgOutput), c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "dkg_pareto_rank": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                c_void_p]),
+    "dkg_pareto_draws": (c_size_t, [c_int, c_int]),
+    "dkg_pareto_variation": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                     POINTER(DkgNsga2Params), c_void_p, c_void_p, c_void_p]),
+    "dkg_pareto_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "dkg_pareto_nsga2": (c_int, [POINTER(DkgOutput), c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                                 POINTER(DkgNsga2Params), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_size_t, c_void_p]),
     "dkg_abi_version": (c_int, []),
     "dkg_last_error": (c_char_p, []),
     "dkg_frag_elems": (c_size_t, [c_int, c_int]),

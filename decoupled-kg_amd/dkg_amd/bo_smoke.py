@@ -33,6 +33,7 @@ checkpoints (``:558-561``); run keys ``eval_separate`` / ``eval_full`` (``main.p
 
 from __future__ import annotations
 
+import time
 from typing import Dict, List, Optional, Sequence
 
 import numpy as np
@@ -70,15 +71,24 @@ def reference_model_config(m: int, bounds, fit_hyperparams: str = "never") -> di
     bnd = torch.as_tensor(bounds, dtype=torch.double).reshape(2, -1)
     return {"bounds": bnd.tolist(), "outputs": [_output_config(10 if i == 0 else 1.1) for i in range(m)],
             "fit_hyperparams": fit_hyperparams}
+METRICS_COLUMNS = ("pfront_hv_lo", "pfront_hv_hi", "pset_hv_lo", "pset_hv_hi", "predicted_scalarperf",
+                   "actual_scalarperf", "cost")  # bo_loop.py:320, 520
+TIMINGS_COLUMNS = ("iteration", "bo", "fit", "metrics")  # bo_loop.py:325-332
 QUERY_COLUMNS = ("iteration", "x", "obj_index", "obj", "obj_true", "cost", "acq_per_cost", "init", "scalarisation")
 
 
 class GPProblem:
     """A ``gp-sample`` test problem: objective i at x is the posterior mean of output i of a fixed GP
-    (``gp_testproblem.py:76-98``), computed by the library's kernels on ``device``."""
+    (``gp_testproblem.py:76-98``), computed by the library's kernels on ``device``.  ``ref_point`` and ``max_hv``
+    (``gp_testproblem.py:49-60``; optional): the hypervolume reference point and the problem's largest hypervolume,
+    as the shared problem file stores them (``DataCatalog.load_shared_gp_test_problem_data``); the metrics of
+    ``run_mobo(metrics=True)`` read ``ref_point``."""
 
-    def __init__(self, gp: ModelListGPState, bounds: Optional[Tensor] = None, device=None):
+    def __init__(self, gp: ModelListGPState, bounds: Optional[Tensor] = None, device=None, ref_point=None,
+                 max_hv: Optional[float] = None):
         self.gp = gp
+        self.ref_point = None if ref_point is None else torch.as_tensor(ref_point, dtype=torch.double).reshape(-1)
+        self.max_hv = None if max_hv is None else float(max_hv)
         d = gp.input_dim
         self.bounds = (torch.stack([torch.zeros(d, dtype=torch.double), torch.ones(d, dtype=torch.double)]) if bounds is None
                        else torch.as_tensor(bounds, dtype=torch.double).reshape(2, d))
@@ -135,7 +145,7 @@ def run_mobo(problem: GPProblem, hyper: Dict[str, Sequence[float]], separate: bo
              spec: Optional[DiscreteKgOptimisationSpec] = None, seed: int = 0,
              catalog: Optional[DataCatalog] = None, run_key: Optional[str] = None,
              fit_hyperparams: str = "never", incremental: bool = False,
-             fit_on_device: bool = False, joint_objectives: bool = False) -> Dict[str, List]:
+             fit_on_device: bool = False, joint_objectives: bool = False, metrics: bool = False) -> Dict[str, List]:
     """``bo_loop.run_mobo`` with the discrete-KG strategy for ``n_iter`` BO steps; returns the
     query history (x, objective index or None for full evaluation, observed values, acquisition).
     With ``catalog`` it also writes the reference's checkpoints and query-history table under
@@ -153,7 +163,21 @@ def run_mobo(problem: GPProblem, hyper: Dict[str, Sequence[float]], separate: bo
     distances differently, so their fits agree to the optimiser's tolerance, not bit for bit, and
     the default keeps the host route's results.  ``joint_objectives`` (``separate`` only; off by default, not the
     reference's search): the query step passes ``joint=True`` to ``optimize_for_single_objective`` -- one
-    ``optimize_acqf`` run on max_t max(KG_t, 0) / cost_t instead of one per objective."""
+    ``optimize_acqf`` run on max_t max(KG_t, 0) / cost_t instead of one per objective.
+
+    ``metrics`` (off by default): after the initial model and after every BO step the loop records what the
+    reference's "Record metrics" blocks do (``bo_loop.py:294-332, 480-520``): the posterior-mean Pareto front of
+    ``N_PARETO_POINTS`` = 100 points (the SMOKE value) by the device NSGA-II
+    (``dkg_amd.pareto.sample_points_on_pareto_front`` on the surrogate with the problem's bounds), saved with
+    ``save_posterior_pareto``; the expected scalarised performance and the hypervolume bounds
+    (``dkg_amd.metrics``; ``problem.ref_point`` is needed); one ``metrics_history`` row (``METRICS_COLUMNS``) and one
+    ``timings_history`` row (``TIMINGS_COLUMNS``), returned in the result and written with ``save_metrics`` /
+    ``save_timings`` at the end (``:558-561``).  The NSGA-II uniforms and the metric's scalarisation weights come
+    from generators of their own seeded from ``seed``, the run and the iteration, so a run with metrics makes
+    exactly the decisions of the run without.  The reference instead draws the weights' seed from the global RNG
+    (``scalarisations_seed=None``), and pygmo seeds itself."""
+    if metrics and problem.ref_point is None:
+        raise ValueError("metrics=True needs problem.ref_point (GPProblem(..., ref_point=...))")
     if fit_hyperparams not in ("never", "once", "always"):
         raise ValueError(f"Unexpected value for fit_hyperparams. Got {fit_hyperparams!r}")
     on = incremental and fit_hyperparams != "always"
@@ -161,14 +185,14 @@ def run_mobo(problem: GPProblem, hyper: Dict[str, Sequence[float]], separate: bo
     try:
         return _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations, spec, seed, catalog,
                          run_key, fit_hyperparams, _fit_device(problem, fit_on_device and fit_hyperparams == "always"),
-                         joint_objectives)
+                         joint_objectives, metrics)
     finally:
         if on:
             set_incremental_state(prev)
 
 
 def _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations, spec, seed, catalog, run_key,
-              fit_hyperparams, fit_device=None, joint_objectives=False) -> Dict[str, List]:
+              fit_hyperparams, fit_device=None, joint_objectives=False, metrics=False) -> Dict[str, List]:
     m, d = problem.num_objectives, problem.gp.input_dim
     # the pipeline's --seed (main.py:235, utils.set_random_seed): every later draw comes from the global RNG, as
     # in the reference -- the initial Sobol points (generate_initial_data, bo_loop.py:48-49: no seed), each
@@ -213,12 +237,37 @@ def _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations,
                                     [t.clone() for t in train_x], [t.clone() for t in train_y],
                                     [t.clone() for t in train_y], problem.bounds.clone())
 
+    metrics_history: List[Dict[str, float]] = []
+    timings_history: List[Dict[str, float]] = []
+
+    def record_metrics(iteration, model, bo_time, fit_time):
+        # "Record metrics" (bo_loop.py:294-332, 480-520); every seed is the block's own
+        from .metrics import (estimate_expected_performance_after_scalarisation,
+                              estimate_hypervolume_from_posterior_mean)
+        from .pareto import N_PARETO_POINTS, sample_points_on_pareto_front
+
+        t0 = time.monotonic()
+        base = 1_000_003 * (2 * int(seed) + (0 if separate else 1)) + 7919 * iteration
+        pset, pfront = sample_points_on_pareto_front(model, problem.bounds, npoints=N_PARETO_POINTS,
+                                                     seed=base + 1, device=problem.device)
+        if catalog is not None:
+            catalog.save_posterior_pareto(run_key, iteration, pset, pfront)
+        perf = estimate_expected_performance_after_scalarisation(pset, pfront, problem, scalarisations_seed=base + 2)
+        hv = estimate_hypervolume_from_posterior_mean(pset, pfront, problem, problem.ref_point)
+        metrics_history.append({**hv, **perf, "cost": float(sum(qh["cost"]))})
+        timings_history.append({"iteration": iteration, "bo": bo_time, "fit": fit_time,
+                                "metrics": time.monotonic() - t0})
+
     for i in range(m):
         for j in range(n_init):
             record(0, x0[j].numpy(), i, y0[j, i], costs[i], float("nan"), True, None)
+    t_fit = time.monotonic()
     model = model_now(first=True)
     checkpoint(0, model)
+    if metrics:
+        record_metrics(0, model, 0, time.monotonic() - t_fit)
     for it in range(n_iter):
+        t_bo = time.monotonic()
         W = sample_simplex(m, n_scalarisations, qmc=True, seed=seed + 1 + it, dtype=torch.double)
         w_row = W[0].numpy().copy() if W.shape[0] == 1 else None
         if separate:
@@ -246,14 +295,23 @@ def _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations,
                 record(it + 1, x[0].numpy(), i, y[i], costs[i], float(acq) / float(sum(costs)), False, w_row)
         hist["x"].append(x[0].tolist())
         hist["acq"].append(float(acq))
+        t_fit = time.monotonic()
         model = model_now()
         checkpoint(it + 1, model)
+        if metrics:
+            record_metrics(it + 1, model, t_fit - t_bo, time.monotonic() - t_fit)
     hist["n_observations"] = [int(t.shape[0]) for t in train_x]
     hist["query_history"] = qh
+    if metrics:
+        hist["metrics_history"] = metrics_history
+        hist["timings_history"] = timings_history
     if catalog is not None:
         import pandas as pd
 
         catalog.save_bo_run(run_key, pd.DataFrame(qh))
+        if metrics:
+            catalog.save_metrics(run_key, pd.DataFrame(metrics_history, columns=list(METRICS_COLUMNS)))
+            catalog.save_timings(run_key, pd.DataFrame(timings_history, columns=list(TIMINGS_COLUMNS)))
         catalog.compress_checkpoints(run_key)
     return hist
 
@@ -261,13 +319,36 @@ def _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations,
 def run_smoke(problem: GPProblem, hyper: Dict[str, Sequence[float]], seed: int = 0,
               catalog: Optional[DataCatalog] = None, fit_hyperparams: str = "never",
               incremental: bool = False, fit_on_device: bool = False,
-              joint_objectives: bool = False) -> Dict[str, Dict]:
+              joint_objectives: bool = False, metrics: bool = False) -> Dict[str, Dict]:
     """``run_pipeline`` under ``SMOKE_TEST`` (``main.py:171-216``): the separate-evaluation run and
     the full-evaluation run, two BO steps each; with ``catalog`` both write the reference's files.
     ``fit_hyperparams = "once"`` fits the hyperparameters first (``main.py:181-182``, saved to the catalog's
     ``hyperparameters.pt`` as the fitted surrogate's state dict) and both runs use them; ``"always"`` refits
     inside the runs.  ``incremental``, ``fit_on_device``: as ``run_mobo``'s (``fit_on_device`` also moves the
-    ``once`` fit's objective to the device); ``joint_objectives``: as ``run_mobo``'s, for the separate run."""
+    ``once`` fit's objective to the device); ``joint_objectives``: as ``run_mobo``'s, for the separate run.
+
+    ``metrics`` (off by default): first the problem's true Pareto front (``main.py:174-175``: the device NSGA-II on
+    the problem itself, ``N_PARETO_POINTS`` points) and the best possible expected scalarised performance on it
+    (``main.py:176-177``, ``nodes/metrics.py:15-23``), written with ``save_true_pareto`` /
+    ``save_problem_max_possible_expected_scalarisation`` when there is a catalog and returned under ``"true_pareto"``
+    / ``"max_possible_expected_scalarisation"``; a problem without ``ref_point`` gets
+    ``calculate_reference_point`` of that front (``gp_testproblem.py:236-247``).  Then both runs record their
+    metrics (``run_mobo``).  The seeds are the metrics' own, so both runs make the decisions they make without."""
+    extra = {}
+    if metrics:
+        from .metrics import (calculate_reference_point,
+                              estimate_best_possible_expected_performance_after_scalarisation)
+        from .pareto import N_PARETO_POINTS, sample_points_on_pareto_front
+
+        base = 1_000_003 * (2 * int(seed)) + 500_009  # between the runs' own seeds (run_mobo)
+        pset, pfront = sample_points_on_pareto_front(problem, npoints=N_PARETO_POINTS, seed=base)
+        best = estimate_best_possible_expected_performance_after_scalarisation(pfront, scalarisations_seed=base + 1)
+        if problem.ref_point is None:
+            problem.ref_point = calculate_reference_point(torch.from_numpy(pfront))
+        if catalog is not None:
+            catalog.save_true_pareto(pset, pfront)
+            catalog.save_problem_max_possible_expected_scalarisation(best)
+        extra = {"true_pareto": (pset, pfront), "max_possible_expected_scalarisation": best}
     if fit_hyperparams == "once":
         torch.manual_seed(seed)
         cfg = reference_model_config(problem.num_objectives, problem.bounds, "once")
@@ -277,9 +358,10 @@ def run_smoke(problem: GPProblem, hyper: Dict[str, Sequence[float]], seed: int =
             y = torch.zeros(1, dtype=torch.double)
             catalog.save_model_hyperparameters(
                 to_state_dict(surrogate([x] * problem.num_objectives, [y] * problem.num_objectives, hyper), cfg))
+    mk = {"metrics": True} if metrics else {}
     return {"separate": run_mobo(problem, hyper, separate=True, seed=seed, catalog=catalog,
                                  fit_hyperparams=fit_hyperparams, incremental=incremental,
-                                 fit_on_device=fit_on_device, joint_objectives=joint_objectives),
+                                 fit_on_device=fit_on_device, joint_objectives=joint_objectives, **mk),
             "full": run_mobo(problem, hyper, separate=False, seed=seed, catalog=catalog,
                              fit_hyperparams=fit_hyperparams, incremental=incremental,
-                             fit_on_device=fit_on_device)}
+                             fit_on_device=fit_on_device, **mk), **extra}

@@ -191,6 +191,89 @@ int dkg_mll_value_grad(const dkg_output* outs, int m, int d, const double* const
                        void* work, size_t work_bytes, double* value, double* grad, double* jitter_used,
                        void* stream);
 
+/* ---- Posterior-mean Pareto front: NSGA-II on the device (dkg_pareto.hip) -----------------------------
+ * The reference samples the Pareto front of the surrogate's posterior mean with pygmo.nsga2(gen=100) at every
+ * BO iteration (modules/pareto/sample.py:16-48; "Record metrics", bo_loop.py:294-332, 480-520) and of the test
+ * problem once (main.py:174).  pygmo is not restated: the operators are the published ones (Deb & Agrawal 1995,
+ * Deb et al. 2002) with pygmo's documented nsga2 defaults, every random number comes from the caller, and no
+ * trajectory parity with pygmo is claimed.  All objectives are maximised.  Limits: m <= DKG_MAX_OUTPUTS,
+ * d <= DKG_MAX_DIM, n <= 1024 per output, population P a multiple of 4 with 8 <= P <= 1024 (DKG_ERR_UNSUPPORTED /
+ * DKG_ERR_ARG otherwise, checked before any device work).  Stream ordered; nothing synchronises. */
+
+/* mean[p*m + i] = y_mean_i + y_std_i (c_i + K(x_p, X_i) alpha_i) for P points x (device [P][d], model inputs):
+ * the posterior mean BoTorchModel.batch_fitness (sample.py:138-144) and GPTestProblem.evaluate_true
+ * (gp_testproblem.py:76-97) take from model.posterior, without the O(P n^2) product Q = K(x, X) R that
+ * dkg_cross_root forms next to it.  Reads n, kernel, the hyperparameters, inv_lengthscale, train_x and alpha
+ * (dkg_prepare_outputs' caches); root_frag and disc_* are not read.  The kernel terms are the cross stage's; a
+ * point's result is one fma chain per lane over the training points and a fixed-order wave reduction, so it has
+ * the same bits whatever P is and whichever row holds the point.  P = 0 is a no-op. */
+int dkg_posterior_mean(const dkg_output* outs, int m, int d, const double* x, int P, double* mean, void* stream);
+
+/* Non-dominated ranks, crowding distances and survivor order of Q <= 2048 points F (device [Q][m], m <= 8).
+ *   dominance: a dominates b iff a >= b in every objective and a > b in at least one (equal points do not
+ *              dominate each other)
+ *   rank     : fronts are peeled in order (Deb et al. 2002) until at least `keep` points carry a rank
+ *              (1 <= keep <= Q; the last front peeled is ranked whole); the rest get rank -1 and crowding 0
+ *   crowd    : within each ranked front, for j = 0 .. m-1 in order: members sorted by (f_j ascending, index
+ *              ascending), the two ends add +inf, an interior member adds (f_j[next] - f_j[prev]) /
+ *              (f_j^max - f_j^min), or 0 when the front's range in j is 0; one subtraction, one division and
+ *              one addition per step, no fused multiply-add
+ *   order    : device int [Q]: the ranked points by (rank ascending, crowding descending, index ascending),
+ *              then -1; its first `keep` entries are the survivors
+ * One workgroup; every loop is bounded by Q.  work / work_bytes: reserved (not read; NULL / 0 are fine). */
+int dkg_pareto_rank(const double* F, int Q, int m, int keep, int* rank, double* crowd, int* order, void* work,
+                    size_t work_bytes, void* stream);
+
+/* NSGA-II's variation parameters; pygmo.nsga2's documented defaults are {0.95, 10, 0.01, 50}.  raw_inputs
+ * (dkg_pareto_nsga2 only): 0 = the model takes inputs normalised to the unit cube with lb / ub (a surrogate,
+ * sample.py:129-130), 1 = it takes the points as they are (a test problem, gp_testproblem.py:76-97). */
+typedef struct dkg_nsga2_params {
+  double cr;     /* crossover probability per pair of children */
+  double eta_c;  /* distribution index of the simulated binary crossover */
+  double m;      /* mutation probability per coordinate */
+  double eta_m;  /* distribution index of the polynomial mutation */
+  int32_t raw_inputs;
+  int32_t reserved;
+} dkg_nsga2_params;
+
+/* Uniforms in [0, 1) one dkg_pareto_variation call reads for a population of P in d dimensions (0 for an odd or
+ * non-positive P or d < 1).  Layout, H = P / 2 pairs of children (children 2k, 2k + 1 from winners 2k, 2k + 1):
+ *   [0, 2P)                  u[2w], u[2w + 1]: the two members floor(u P) of winner w's tournament
+ *   [2P, 2P + H)             pair k crosses over iff u < cr
+ *   then [H][d][3]           per (pair, coordinate): the coordinate is crossed iff u0 < 0.5 (and the parents differ
+ *                            by more than 1e-14), u1 the spread draw, the two children are swapped iff u2 < 0.5
+ *   then [P][d][2]           per (child, coordinate): mutated iff u0 < m, u1 the perturbation draw */
+size_t dkg_pareto_draws(int P, int d);
+
+/* P children (device [P][d]) of a ranked population X (device [P][d]; rank, crowd: device [P], every member
+ * ranked, as dkg_pareto_rank with keep = P leaves them).  Selection: binary tournament between two members drawn
+ * with replacement; the lower rank wins, then the larger crowding, then the first drawn.  Crossover: bounded
+ * simulated binary crossover on consecutive winners; mutation: bounded polynomial mutation; children are clipped
+ * into [lb, ub] (device [d] each).  No random number generator runs on the device: `uniforms` (device,
+ * dkg_pareto_draws(P, d) doubles in [0, 1)) is the only randomness.  With cr = 0 and m = 0 every child is a
+ * bit-exact copy of its tournament winner. */
+int dkg_pareto_variation(const double* X, const int* rank, const double* crowd, int P, int d, const double* lb,
+                         const double* ub, const dkg_nsga2_params* prm, const double* uniforms, double* children,
+                         void* stream);
+
+/* Bytes of device scratch dkg_pareto_nsga2 needs (0 outside the limits above). */
+size_t dkg_pareto_workspace(int P, int d, int m);
+
+/* The whole evolution, no host synchronisation inside: what pop = algo.evolve(pop) does at sample.py:40-44.
+ *   uniforms: device, P d + gens * dkg_pareto_draws(P, d) doubles in [0, 1)
+ *   generation 0: X = lb + u (ub - lb) from the first P d uniforms, F = the posterior mean there, ranked with
+ *                 keep = P (X keeps the sampled order)
+ *   generation g >= 1, from the uniforms at P d + (g - 1) dkg_pareto_draws(P, d):
+ *     dkg_pareto_variation -> P children; dkg_posterior_mean of the children (of (x - lb) / (ub - lb) unless
+ *     prm->raw_inputs); dkg_pareto_rank of the 2P points [parents; children] with keep = P; the survivors, in
+ *     `order` order, become X, F, rank, crowd ((mu + lambda) elitist survival)
+ *   X [P][d], F [P][m], rank [P], crowd [P]: device, the final population and its ranking
+ *   work: device scratch of dkg_pareto_workspace(P, d, m) bytes (DKG_ERR_WORKSPACE when short)
+ * Bit for bit what the same sequence of the three stage entries gives. */
+int dkg_pareto_nsga2(const dkg_output* outs, int m, int d, const double* lb, const double* ub, int P, int gens,
+                     const dkg_nsga2_params* prm, const double* uniforms, double* X, double* F, int* rank,
+                     double* crowd, void* work, size_t work_bytes, void* stream);
+
 /* Bytes of scratch dkg_forward needs for (m outputs, N points, B candidates, S weights). */
 size_t dkg_forward_workspace(const dkg_output* outs, int m, int N, int B, int S);
 
