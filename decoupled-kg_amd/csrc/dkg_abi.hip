@@ -188,6 +188,31 @@ int check_targets(const int* targets, int T, int m) {
   return DKG_OK;
 }
 
+// Where a gradient plan's envelope takes the candidate's q_i / J_i rows from: 0 staged in LDS, 1 global rows
+// (envelope_rows_kernel, always streaming), or the refusal's status negated.  Without DKG_PLAN_GRAD_GLOBAL_ROWS /
+// DKG_PLAN_FORCE_GLOBAL_ROWS this is the staged plan or its refusal; DKG_PLAN_GRAD_GLOBAL_ROWS changes the
+// refusal alone.  Host arithmetic only (dkg_plan_grad_rows).
+int grad_rows_rule(int m, int N, int sw, int S, int d, int max_np, int flags) {
+  const bool fits = envelope_grad_lds_bytes(m, N, sw, S, d, max_np, true) <= 160 * 1024;
+  if (fits && !(flags & DKG_PLAN_FORCE_GLOBAL_ROWS)) return 0;
+  if ((flags & (DKG_PLAN_GRAD_GLOBAL_ROWS | DKG_PLAN_FORCE_GLOBAL_ROWS)) &&
+      envelope_grad_rows_lds_bytes(m, N, sw, S, max_np) <= 160 * 1024)
+    return 1;
+  return -fail(DKG_ERR_UNSUPPORTED, "gradient: m=%d outputs, n=%d, d=%d exceed the envelope stage's LDS", m, max_np, d);
+}
+
+// The flag checks of a plan, in build_plan's order.
+int check_plan_flags(int flags) {
+  if (flags & ~(DKG_PLAN_GRAD | DKG_PLAN_FORCE_WALK | DKG_PLAN_F32 | DKG_PLAN_FUSED | DKG_PLAN_NO_CHAIN |
+                DKG_PLAN_GRAD_GLOBAL_ROWS | DKG_PLAN_FORCE_GLOBAL_ROWS))
+    return fail(DKG_ERR_ARG, "unknown plan flags 0x%x", flags);
+  if ((flags & (DKG_PLAN_GRAD_GLOBAL_ROWS | DKG_PLAN_FORCE_GLOBAL_ROWS)) && !(flags & DKG_PLAN_GRAD))
+    return fail(DKG_ERR_ARG, "plan flags 0x%x: the global-rows flags need DKG_PLAN_GRAD", flags);
+  if ((flags & DKG_PLAN_GRAD) && (flags & DKG_PLAN_F32))
+    return fail(DKG_ERR_UNSUPPORTED, "the fp32 plan (DKG_PLAN_F32) is forward only; the gradient runs in fp64");
+  return DKG_OK;
+}
+
 // targets == nullptr: the single-target plan of `target`.
 int build_plan(const dkg_output* outs, int m, int d, const double* disc, int N, const double* weights, int S,
                int target, int max_B, void* workspace, size_t workspace_bytes, Plan* P, int flags = 0,
@@ -212,20 +237,17 @@ int build_plan(const dkg_output* outs, int m, int d, const double* disc, int N, 
   // the register slots; otherwise it streams them from global memory
   const bool want_grad = (flags & DKG_PLAN_GRAD) != 0;
   bool stream = N + 1 > 64 * 33 || envelope_lds_bytes(m, N, sw, S, false) > 160 * 1024 ||
-                (want_grad && envelope_grad_lds_bytes(m, N, sw, S, d, max_np, false) > 160 * 1024);
+                (want_grad && envelope_grad_lds_bytes(m, N, sw, S, d, max_np, false) > 160 * 1024) ||
+                (want_grad && (flags & DKG_PLAN_FORCE_GLOBAL_ROWS));
   if (envelope_lds_bytes(m, N, sw, S, true) > 160 * 1024)
     return fail(DKG_ERR_UNSUPPORTED, "S=%d x m=%d weights exceed the envelope stage's LDS", S, m);
   if (!weights || !workspace || (N > 0 && !disc)) return fail(DKG_ERR_ARG, "NULL data pointer");
   for (int i = 0; i < m; ++i)
     if (N > 0 && (!outs[i].disc_frag || !outs[i].disc_mean))
       return fail(DKG_ERR_ARG, "output %d: discretisation caches missing", i);
-  if (flags & ~(DKG_PLAN_GRAD | DKG_PLAN_FORCE_WALK | DKG_PLAN_F32 | DKG_PLAN_FUSED | DKG_PLAN_NO_CHAIN))
-    return fail(DKG_ERR_ARG, "unknown plan flags 0x%x", flags);
-  if (want_grad && (flags & DKG_PLAN_F32))
-    return fail(DKG_ERR_UNSUPPORTED, "the fp32 plan (DKG_PLAN_F32) is forward only; the gradient runs in fp64");
-  if (want_grad && envelope_grad_lds_bytes(m, N, sw, S, d, max_np, true) > 160 * 1024)
-    return fail(DKG_ERR_UNSUPPORTED, "gradient: m=%d outputs, n=%d, d=%d exceed the envelope stage's LDS", m, max_np,
-                d);
+  if ((st = check_plan_flags(flags))) return st;
+  const int grows = want_grad ? grad_rows_rule(m, N, sw, S, d, max_np, flags) : 0;
+  if (grows < 0) return -grows;
   const WsLayout L = layout(outs, m, N, max_B, S, d, flags, T);
   if (workspace_bytes < L.total)
     return fail(DKG_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, L.total);
@@ -250,6 +272,7 @@ int build_plan(const dkg_output* outs, int m, int d, const double* disc, int N, 
   P->grad = want_grad ? 1 : 0;
   P->f32 = (flags & DKG_PLAN_F32) ? 1 : 0;
   P->stream = stream ? 1 : 0;
+  P->grad_rows = grows;  // 1 only where stream is set: by the force flag, or because the staged rows do not fit
   P->bpad = pad16(std::max(max_B, 1));
   for (int i = 0; i < m; ++i) {
     P->o[i] = outs[i];
@@ -785,6 +808,21 @@ size_t dkg_plan_workspace(const dkg_output* outs, int m, int d, int N, int max_B
   return layout(outs, m, N, max_B, S, d, flags).total;
 }
 
+int dkg_plan_grad_rows(const dkg_output* outs, int m, int d, int N, int S, int flags) {
+  int st = check_outputs(outs, m, d);
+  if (st) return -st;
+  if (N < 0) return -fail(DKG_ERR_ARG, "negative size N=%d", N);
+  if (S < 1) return -fail(DKG_ERR_ARG, "S=%d scalarisations", S);
+  if (N > (1 << 22)) return -fail(DKG_ERR_UNSUPPORTED, "N=%d discretisation points (supported <= %d)", N, 1 << 22);
+  int sw, split;
+  envelope_geometry(S, &sw, &split);
+  if (envelope_lds_bytes(m, N, sw, S, true) > 160 * 1024)
+    return -fail(DKG_ERR_UNSUPPORTED, "S=%d x m=%d weights exceed the envelope stage's LDS", S, m);
+  if ((st = check_plan_flags(flags))) return -st;
+  if (!(flags & DKG_PLAN_GRAD)) return -fail(DKG_ERR_ARG, "dkg_plan_grad_rows: flags 0x%x lack DKG_PLAN_GRAD", flags);
+  return grad_rows_rule(m, N, sw, S, d, max_np_of(outs, m), flags);
+}
+
 int dkg_plan_init(const dkg_output* outs, int m, int d, const double* disc, int N, const double* weights, int S,
                   int target, int max_B, int flags, void* workspace, size_t workspace_bytes, void* host_plan,
                   void* dev_plan, void* stream) {
@@ -894,6 +932,10 @@ int dkg_plan_status(const void* host_plan, int* err, int reset, void* stream) {
 }
 
 int dkg_plan_fused(const void* host_plan) { return host_plan ? static_cast<const Plan*>(host_plan)->fused : 0; }
+
+int dkg_plan_grad_rows_of(const void* host_plan) {
+  return host_plan ? static_cast<const Plan*>(host_plan)->grad_rows : 0;
+}
 
 int dkg_plan_hull_sizes(const void* host_plan, int* out, int B, void* stream) {
   if (!host_plan || !out) return fail(DKG_ERR_ARG, "NULL pointer");

@@ -1471,7 +1471,11 @@ __host__ __device__ constexpr int env_waves_per_eu(int maxl, int m, bool grad, b
 // and the weights arrive as arguments, so the first DMA issues after a
 // single kernel-argument load instead of a pointer chase through the plan.
 // MT (envelope_targets_kernel): item (tau, b) of a plan of ntgt targets, its target in the arguments.
-template <int MAXL, int M, bool GRAD, bool STREAM, bool HO = false, bool MT = false>
+// GROWS (envelope_rows_kernel, streaming GRAD only): "global rows": the candidate's q_i / J_i rows are not staged
+// in LDS (no qrow / jrow block) but read where the cross stage left them (Plan::qxrm / jq), by the same lanes
+// in the same column order into the same fma chains: the staged-rows streaming GRAD kernel's bits, for models
+// whose rows do not fit in LDS.
+template <int MAXL, int M, bool GRAD, bool STREAM, bool HO = false, bool MT = false, bool GROWS = false>
 __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B, double* __restrict__ kg,
                                               double* __restrict__ pairs_out, int dst,
                                               const double* __restrict__ xnew, double* __restrict__ dkg,
@@ -1483,6 +1487,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
                                               const Handoff* ho = nullptr, double* __restrict__ hout = nullptr,
                                               int tau = 0, int ntgt = 1, int target_mt = -1) {
   static_assert(!HO || (!GRAD && !STREAM), "the fused forward stages its lines (no gradient, no streaming)");
+  static_assert(!GROWS || (GRAD && STREAM), "global rows: the streaming gradient envelope only");
   // per output i: y_std, y_mean, noise, outputscale, noiseless variance at x_b, mean at x_b (model space),
   // and line 0's inputs: the mean and slope component it is built from (x_b's own, or, when x_b coincides
   // with a discretisation point (Plan::dup), that line's record: line 0 is then its exact copy)
@@ -1542,9 +1547,13 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
   if constexpr (GRAD) {
     double* gb = sbuf + (size_t)SW * 2 * LC;
     sidx = reinterpret_cast<int*>(gb);
-    qrow = gb + (SW * ENV_CAP + 1) / 2;
-    jrow = qrow + (size_t)M * NPS;                   // rows of stride NPS: whole DMA pieces
-    sgv = jrow + (size_t)M * d * NPS;               // [M][16]  d v_i / dx
+    if constexpr (GROWS) {
+      sgv = gb + (SW * ENV_CAP + 1) / 2;             // no qrow / jrow: the rows stay in global memory
+    } else {
+      qrow = gb + (SW * ENV_CAP + 1) / 2;
+      jrow = qrow + (size_t)M * NPS;                 // rows of stride NPS: whole DMA pieces
+      sgv = jrow + (size_t)M * d * NPS;              // [M][16]  d v_i / dx
+    }
     sgm = sgv + M * DKG_MAX_DIM;                     // [M][16]  d mu_i / dx
     sgw = sgm + M * DKG_MAX_DIM;                     // [SW][64] per wave: gacc | ga0 | gvv | gtot
     sx = sgw + SW * 64;                              // [16]     x_b
@@ -1579,7 +1588,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
     dma_to_lds(mu_src[0], lmu, N * MP, wave, SW, lane_k);
     if constexpr (!HO) dma_to_lds(cv_src[0], lcv, N * MP, wave, SW, lane_k);
   }
-  if constexpr (GRAD) {
+  if constexpr (GRAD && !GROWS) {
     // the candidate's q_i and J_i rows (row-major in the workspace) by LDS-DMA with the line data, so
     // they cost no extra memory round trip; entries npi .. NP-1 are zeroed after the wait
 #pragma unroll
@@ -1685,21 +1694,23 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
       }
     }
     // rows of outputs with fewer (padded) training points than the widest: zero the tail the DMA filled
-    bool tail = false;
+    if constexpr (!GROWS) {
+      bool tail = false;
 #pragma unroll
-    for (int i = 0; i < M; ++i) {
-      if (i < m) {
-        const int npi = pad16(P->o[i].n);
-        if (npi < NP) {
-          tail = true;
-          for (int c = npi + (int)threadIdx.x; c < NP; c += blockDim.x) {
-            qrow[(size_t)i * NPS + c] = 0.0;
-            for (int dd = 0; dd < d; ++dd) jrow[((size_t)i * d + dd) * NPS + c] = 0.0;
+      for (int i = 0; i < M; ++i) {
+        if (i < m) {
+          const int npi = pad16(P->o[i].n);
+          if (npi < NP) {
+            tail = true;
+            for (int c = npi + (int)threadIdx.x; c < NP; c += blockDim.x) {
+              qrow[(size_t)i * NPS + c] = 0.0;
+              for (int dd = 0; dd < d; ++dd) jrow[((size_t)i * d + dd) * NPS + c] = 0.0;
+            }
           }
         }
       }
+      if (tail) __syncthreads();  // uniform
     }
-    if (tail) __syncthreads();  // uniform
   }
   if (!GRAD) KST(st, 3);
 
@@ -1725,7 +1736,19 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
     for (int pidx = wave; pidx < m * d; pidx += SW) {
       const int i = pidx / d, dd = pidx % d;
       double acc = 0.0;
-      for (int c = lane_k; c < NP; c += 64) acc = fma(jrow[((size_t)i * d + dd) * NPS + c], qrow[(size_t)i * NPS + c], acc);
+      if constexpr (GROWS) {
+        // the staged rows' sum over all of NP: columns npi .. NP-1 (the tail the staged body zeroes) enter as 0
+        const int npi = pad16(P->o[i].n);
+        const double* qg = P->qxrm[i] + (size_t)b * npi;
+        const double* jg = P->jq[i] + ((size_t)dd * bpad + b) * npi;
+        for (int c = lane_k; c < NP; c += 64) {
+          const int cc = min(c, npi - 1);
+          const double jv = (c < npi) ? jg[cc] : 0.0, qv = (c < npi) ? qg[cc] : 0.0;
+          acc = fma(jv, qv, acc);
+        }
+      } else {
+        for (int c = lane_k; c < NP; c += 64) acc = fma(jrow[((size_t)i * d + dd) * NPS + c], qrow[(size_t)i * NPS + c], acc);
+      }
       acc = wave_sum(acc);
       if (lane_k == 0) sgv[i * DKG_MAX_DIM + dd] = -2.0 * acc;
     }
@@ -2164,7 +2187,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
           for (int i = 0; i < M; ++i) {
             if (i < m && wb[i] != 0.0) {
               for (int dd = 0; dd < d; ++dd) {
-                const double* jr = jrow + ((size_t)i * d + dd) * NPS;
+                const double* jr = GROWS ? P->jq[i] + ((size_t)dd * bpad + b) * npo[i] : jrow + ((size_t)i * d + dd) * NPS;
                 double acc = 0.0;
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
@@ -2195,7 +2218,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
                 if (c + 64 * q < npi) uw[c + 64 * q] = u[q] * wb[i];
             }
             for (int dd = 0; dd < d; ++dd) {
-              const double* jr = jrow + ((size_t)i * d + dd) * NPS;
+              const double* jr = GROWS ? P->jq[i] + ((size_t)dd * bpad + b) * npi : jrow + ((size_t)i * d + dd) * NPS;
               double acc = 0.0;
               for (int c = lane; c < npi; c += 64) acc = fma(jr[c], uw[c], acc);
               acc = wave_sum(acc);
@@ -2546,6 +2569,52 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(env_waves_p
                                                     target_of(tpack, tau));
 }
 
+// The streaming value+gradient envelope with global rows (envelope_body GROWS; DKG_PLAN_GRAD_GLOBAL_ROWS): kernels of
+// their own, so every other instantiation keeps its name and its code.  One target, and items (tau, b).
+template <int M>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(env_waves_per_eu(STREAM_CHUNK, M, true, true)))) void envelope_rows_kernel(const Plan* __restrict__ P, int B, double* __restrict__ kg,
+                                                       double* __restrict__ pairs_out, int dst,
+                                                       const double* __restrict__ xnew, double* __restrict__ dkg,
+                                                       const double* __restrict__ mu_all,
+                                                       const double* __restrict__ cov_all,
+                                                       const double* __restrict__ var_all,
+                                                       const double* __restrict__ mux_all,
+                                                       const double* __restrict__ wts,
+                                                       const int* __restrict__ dupv, long long cov_stride,
+                                                       int bpad, double* __restrict__ hout, int split) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  if (DKG_ABLATIONS && (__builtin_amdgcn_readfirstlane(P->debug_env) & 2)) return;  // ablation: empty envelope stage
+  int b, g;
+  if (!xcd_group(blockIdx.x, B, split, b, g)) return;
+  envelope_body<STREAM_CHUNK, M, true, true, false, false, true>(P, B, kg, pairs_out, dst, xnew, dkg, mu_all, cov_all,
+                                                                 var_all, mux_all, wts, dupv, cov_stride, bpad, b, g,
+                                                                 split, smem, kst_slot(dst, P, 2), nullptr, hout);
+}
+
+template <int M>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(env_waves_per_eu(STREAM_CHUNK, M, true, true)))) void envelope_rows_targets_kernel(const Plan* __restrict__ P, int B, double* __restrict__ kg,
+                                                       double* __restrict__ pairs_out, int dst,
+                                                       const double* __restrict__ xnew, double* __restrict__ dkg,
+                                                       const double* __restrict__ mu_all,
+                                                       const double* __restrict__ cov_all,
+                                                       const double* __restrict__ var_all,
+                                                       const double* __restrict__ mux_all,
+                                                       const double* __restrict__ wts,
+                                                       const int* __restrict__ dupv, long long cov_stride,
+                                                       int bpad, double* __restrict__ hout, int split,
+                                                       int ntgt, unsigned long long tpack) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  if (DKG_ABLATIONS && (__builtin_amdgcn_readfirstlane(P->debug_env) & 2)) return;  // ablation: empty envelope stage
+  int b, g;
+  if (!xcd_group(blockIdx.x, B, split * ntgt, b, g)) return;
+  const int tau = g / split;
+  g -= tau * split;
+  envelope_body<STREAM_CHUNK, M, true, true, false, true, true>(P, B, kg, pairs_out, dst, xnew, dkg, mu_all, cov_all,
+                                                                var_all, mux_all, wts, dupv, cov_stride, bpad, b, g,
+                                                                split, smem, kst_slot(dst, P, 2), nullptr, hout, tau,
+                                                                ntgt, target_of(tpack, tau));
+}
+
 // The lines of every (candidate, scalarisation) pair of the plan's last
 // cross / covariance stages, as the envelope builds them (dkg_plan_lines):
 // a_out / b_out [B][S][N + 1], line 0 the candidate itself.  Grid (B, S).
@@ -2633,12 +2702,31 @@ hipError_t launch_env_t(const EnvLaunch& a) {
   return hipGetLastError();
 }
 
+// The global-rows streaming value+gradient envelope of bucket M (Plan::grad_rows).
+template <int M>
+hipError_t launch_env_rows_t(const EnvLaunch& a) {
+  const Plan& h = *a.host;
+  if (h.ntgt > 1) {
+    raise_lds_limit((const void*)envelope_rows_targets_kernel<M>, a.lds);
+    hipLaunchKernelGGL((envelope_rows_targets_kernel<M>), a.grid, a.block, a.lds, a.s, a.dev, a.B, a.kg, a.pairs,
+                       a.dst, a.xnew, a.dkg, h.mu_all, h.cov_all, h.var_all, h.mux_all, h.weights, h.dup,
+                       (long long)h.cov_stride, h.bpad, a.hout, h.split, h.ntgt, h.tpack);
+    return hipGetLastError();
+  }
+  raise_lds_limit((const void*)envelope_rows_kernel<M>, a.lds);
+  hipLaunchKernelGGL((envelope_rows_kernel<M>), a.grid, a.block, a.lds, a.s, a.dev, a.B, a.kg, a.pairs, a.dst, a.xnew,
+                     a.dkg, h.mu_all, h.cov_all, h.var_all, h.mux_all, h.weights, h.dup, (long long)h.cov_stride,
+                     h.bpad, a.hout, h.split);
+  return hipGetLastError();
+}
 
 // One output bucket M: picks the line-slot instantiation (MAXL) or the
 // streaming kernel.  Defined in dkg_env_m<M>.hip (one translation unit per
 // bucket, compiled in parallel).
 template <int M, bool GRAD>
 hipError_t launch_env_bucket(int lines, bool stream, const EnvLaunch& a) {
+  if constexpr (GRAD)
+    if (stream && a.host->grad_rows) return launch_env_rows_t<M>(a);
   if (stream) return launch_env_t<STREAM_CHUNK, M, GRAD, true>(a);
   if (lines <= 64 * 2) return launch_env_t<2, M, GRAD, false>(a);
   if (lines <= 64 * 8) return launch_env_t<8, M, GRAD, false>(a);

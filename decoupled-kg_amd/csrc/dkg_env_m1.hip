@@ -1,4 +1,5 @@
-// envelope_kernel instantiations for output bucket M = 1 (forward and gradient), and the fused
+// envelope_kernel instantiations for output bucket M = 1 (forward, gradient, and the streaming gradient with
+// global rows: envelope_rows_kernel, picked by launch_env_bucket on Plan::grad_rows), and the fused
 // one-launch forward of the same bucket (dkg_fused.h).
 #include "dkg_fused.h"
 

@@ -120,6 +120,9 @@ struct Plan {
   // tlist for the envelope kernel's arguments: 4 bits per target, tlist[tau] + 1 at bits 4 tau (target_of), so
   // a workgroup has its target with the argument load instead of a dependent load through the plan
   unsigned long long tpack;
+  // DKG_PLAN_GRAD_GLOBAL_ROWS / DKG_PLAN_FORCE_GLOBAL_ROWS: the (streaming) gradient envelope reads the
+  // candidate's q_i / J_i rows from qxrm / jq instead of staging them in LDS (envelope_rows_kernel)
+  int32_t grad_rows;
 };
 
 __host__ __device__ inline int target_of(unsigned long long tpack, int tau) {
@@ -218,6 +221,8 @@ struct XArg {
 hipError_t launch_forward_grad(const Plan& h, const Plan* dev, const double* xnew, int B, double* kg, double* dkg,
                                hipStream_t s, const XArg* xa = nullptr, double* hout = nullptr);
 size_t envelope_grad_lds_bytes(int m, int N, int waves, int S, int d, int max_np, bool stream);
+// The same for the global-rows variant (streaming only): no q_i / J_i rows.
+size_t envelope_grad_rows_lds_bytes(int m, int N, int waves, int S, int max_np);
 // One stage of the forward (0 cross_root, 1 posterior_cov, 2 envelope) on stream s.  geom_B (0: B) is the
 // batch size the covariance block shape is chosen for: a launch over K batches of geom_B candidates
 // (dkg_plan_forward_batches) takes the blocks of one geom_B forward, so its results are those of K forwards.

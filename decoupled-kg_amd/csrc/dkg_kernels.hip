@@ -408,6 +408,16 @@ size_t envelope_grad_lds_bytes(int m, int N, int waves, int S, int d, int max_np
   return envelope_lds_bytes(m, N, waves, S, stream, true) + extra * sizeof(double);
 }
 
+// Global rows (envelope_body GROWS): the streaming gradient envelope's layout without the M (d + 1) rows of
+// stage_len(max_np) doubles; what grows with n is the per-wave u_i vector alone.
+size_t envelope_grad_rows_lds_bytes(int m, int N, int waves, int S, int max_np) {
+  const int M = outputs_bucket(m);
+  const size_t extra = (size_t)(waves * ENV_CAP + 1) / 2 + 2 * (size_t)M * DKG_MAX_DIM + (size_t)waves * 64 +
+                       DKG_MAX_DIM + (size_t)M * DKG_MAX_DIM + (size_t)waves * (HCAP + max_np + ENV_CAP) +
+                       (size_t)(waves * HCAP + 1) / 2;
+  return envelope_lds_bytes(m, N, waves, S, true, true) + extra * sizeof(double);
+}
+
 // ---------------------------------------------------------------------------
 // lines_kg_kernel: KG = E[max_k (a_k + b_k Z)] - max_k a_k for P independent
 // sets of L lines (row-major [P][L]); one wave per set.  Exposes the envelope
@@ -897,8 +907,9 @@ hipError_t launch_forward_grad(const Plan& h, const Plan* dev, const double* xne
   if (e != hipSuccess) return e;
   if ((e = launch_stage(h, dev, xnew, B, kg, nullptr, s, 1)) != hipSuccess) return e;  // cov rows, variances
   EnvLaunch a{&h, dev, B, kg, nullptr, dim3(xcd_group_size(B, h.split * h.ntgt)), dim3(h.sw * WAVE),
-              envelope_grad_lds_bytes(h.m, h.N, h.sw, h.S, h.d, h.max_np, h.stream != 0), s, h.debug_stamp, xnew, dkg,
-              hout};
+              h.grad_rows ? envelope_grad_rows_lds_bytes(h.m, h.N, h.sw, h.S, h.max_np)
+                          : envelope_grad_lds_bytes(h.m, h.N, h.sw, h.S, h.d, h.max_np, h.stream != 0),
+              s, h.debug_stamp, xnew, dkg, hout};
   return launch_env<true>(h, a);
 }
 

@@ -17,7 +17,14 @@ from .discretekg import (
     t_batch_mode_transform,
 )
 from .errors import BotorchTensorDimensionError, DkgNativeError, UnsupportedError
-from .gp_state import DeviceGPState, reset_state_stats, set_incremental_state, state_stats
+from .gp_state import (
+    DeviceGPState,
+    gradient_rows,
+    reset_state_stats,
+    set_gradient_rows,
+    set_incremental_state,
+    state_stats,
+)
 from .metrics import (
     calculate_reference_point,
     estimate_best_possible_expected_performance_after_scalarisation,
@@ -45,6 +52,8 @@ __all__ = [
     "UnsupportedError",
     "DeviceGPState",
     "set_incremental_state",
+    "set_gradient_rows",
+    "gradient_rows",
     "state_stats",
     "reset_state_stats",
     "ModelListGPState",

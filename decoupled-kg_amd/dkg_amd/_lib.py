@@ -24,6 +24,8 @@ DKG_PLAN_FORCE_WALK = 2  # test hook: envelope overflow path for every pair
 DKG_PLAN_F32 = 4  # fp32 contractions (BASELINE configs[4]); forward only
 DKG_PLAN_FUSED = 8  # the forward as one launch with in-launch hand-offs (dkg_fused.h); not the default
 DKG_PLAN_NO_CHAIN = 16  # test hook: the streaming envelope's list-overflow path (no sample chain) for every pair
+DKG_PLAN_GRAD_GLOBAL_ROWS = 32  # with GRAD: read the Q_X / J rows from the workspace where they do not fit in LDS
+DKG_PLAN_FORCE_GLOBAL_ROWS = 128  # test hook, with GRAD: the streaming global-rows envelope on any shape
 # dkg_debug_cov_kernels: the opt-in fp64 covariance block kernels (same bits as the defaults)
 DKG_COV_ENABLE_BLK, DKG_COV_ENABLE_REC2, DKG_COV_ENABLE_REG = 1, 2, 4
 MAX_OUTPUTS = 8
@@ -123,6 +125,8 @@ SIGNATURES = {
     "dkg_plan_hull_sizes": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "dkg_plan_status": (c_int, [c_void_p, POINTER(c_int), c_int, c_void_p]),
     "dkg_plan_fused": (c_int, [c_void_p]),
+    "dkg_plan_grad_rows": (c_int, [POINTER(DkgOutput), c_int, c_int, c_int, c_int, c_int]),
+    "dkg_plan_grad_rows_of": (c_int, [c_void_p]),
     "dkg_lines_kg": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dkg_epigraph": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dkg_pwl_expectation": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
@@ -171,6 +175,8 @@ def check(status: int, what: str) -> None:
     if status == DKG_ERR_ARG:
         raise BotorchTensorDimensionError(msg)
     if status == DKG_ERR_UNSUPPORTED:
+        if "gradient:" in msg and "envelope stage's LDS" in msg:
+            msg += '. dkg_amd.set_gradient_rows("auto") builds a plan that reads those rows from global memory instead.'
         raise UnsupportedError(msg)
     if status == DKG_ERR_NO_LINES:
         raise ValueError(msg)

@@ -175,7 +175,10 @@ def run_mobo(problem: GPProblem, hyper: Dict[str, Sequence[float]], separate: bo
     ``save_timings`` at the end (``:558-561``).  The NSGA-II uniforms and the metric's scalarisation weights come
     from generators of their own seeded from ``seed``, the run and the iteration, so a run with metrics makes
     exactly the decisions of the run without.  The reference instead draws the weights' seed from the global RNG
-    (``scalarisations_seed=None``), and pygmo seeds itself."""
+    (``scalarisations_seed=None``), and pygmo seeds itself.
+
+    Where the gradient plans take their rows from follows the module default (``dkg_amd.set_gradient_rows``);
+    there is no argument for it here."""
     if metrics and problem.ref_point is None:
         raise ValueError("metrics=True needs problem.ref_point (GPProblem(..., ref_point=...))")
     if fit_hyperparams not in ("never", "once", "always"):
@@ -333,7 +336,9 @@ def run_smoke(problem: GPProblem, hyper: Dict[str, Sequence[float]], seed: int =
     ``save_problem_max_possible_expected_scalarisation`` when there is a catalog and returned under ``"true_pareto"``
     / ``"max_possible_expected_scalarisation"``; a problem without ``ref_point`` gets
     ``calculate_reference_point`` of that front (``gp_testproblem.py:236-247``).  Then both runs record their
-    metrics (``run_mobo``).  The seeds are the metrics' own, so both runs make the decisions they make without."""
+    metrics (``run_mobo``).  The seeds are the metrics' own, so both runs make the decisions they make without.
+
+    The gradient-rows mode of both runs is the module default (``dkg_amd.set_gradient_rows``), as in ``run_mobo``."""
     extra = {}
     if metrics:
         from .metrics import (calculate_reference_point,

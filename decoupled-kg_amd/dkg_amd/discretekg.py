@@ -240,7 +240,7 @@ class _HostForwardFn(torch.autograd.Function):
         B = xs.numel() // d
         if ctx.needs_input_grad[0]:
             plan = acq._plan_grad
-            if plan is None or plan.max_B < B:
+            if plan is None or plan.max_B < B or plan.grad_rows != acq._rows_mode():
                 plan = acq._plan_for(B, grad=True)
             kg, dkg = plan.forward_grad_host_shaped(xs, B, batch, X.shape)
             ctx.save_for_backward(dkg)
@@ -343,7 +343,8 @@ class DiscreteKnowledgeGradient(_Base):
         return cls(model, x_disc, scalarisation_weights, target_output_ix)
 
     def __init__(self, model, x_discretisation: Tensor, scalarisation_weights: Optional[Tensor] = None,
-                 target_output_ix: Optional[int] = None, device=None, precision: str = "fp64"):
+                 target_output_ix: Optional[int] = None, device=None, precision: str = "fp64",
+                 gradient_rows: Optional[str] = None):
         if _HAVE_BOTORCH:  # pragma: no cover
             super().__init__(model=model)
         else:
@@ -374,6 +375,11 @@ class DiscreteKnowledgeGradient(_Base):
         # "fp32": the two contractions of the forward in fp32 MFMA (include/dkg.h DKG_PLAN_F32;
         # BASELINE configs[4]); not a reference mode, forward only
         self.precision = precision
+        # where the gradient plans take the candidates' Q_X / J rows from (ForwardPlan grad_rows): "staged",
+        # "auto" or "global"; None: the module default (dkg_amd.set_gradient_rows), read at every call
+        if gradient_rows is not None:
+            gp_state.check_gradient_rows(gradient_rows)
+        self.gradient_rows = gradient_rows
         self.x_discretisation = x_discretisation
         self.scalarisation_weights = scalarisation_weights
         self.target_output_ix = target_output_ix
@@ -394,8 +400,11 @@ class DiscreteKnowledgeGradient(_Base):
         self._wfp = _weights_fingerprint(scalarisation_weights)
         self._W = scalarisation_weights.detach().to(self._state.device, torch.double, copy=True).contiguous()
         self._plan = None
+        # the gradient plan of the last call, and the gradient plans by gradient-rows mode
         self._plan_grad = None
-        # the plans of several targets (forward_targets), by (target tuple, with gradient buffers)
+        self._plans_grad = {}
+        # the plans of several targets (forward_targets), by (target tuple, with gradient buffers) and, gradient
+        # plans of a mode other than "staged", the mode
         self._plans_targets = {}
 
     def _refresh(self):
@@ -409,6 +418,7 @@ class DiscreteKnowledgeGradient(_Base):
                                        owner=self.model)
             self._plan = None
             self._plan_grad = None
+            self._plans_grad = {}
             self._plans_targets = {}
             self._fp = fp
         wfp = _weights_fingerprint(self.scalarisation_weights)
@@ -420,6 +430,7 @@ class DiscreteKnowledgeGradient(_Base):
             self._W = w.detach().to(self._state.device, torch.double, copy=True).contiguous()
             self._plan = None
             self._plan_grad = None
+            self._plans_grad = {}
             self._plans_targets = {}
             self._wfp = wfp
 
@@ -430,9 +441,17 @@ class DiscreteKnowledgeGradient(_Base):
         clear_state_cache()
         self._fp = None
 
+    def _rows_mode(self) -> str:
+        """The gradient-rows mode of this acquisition's gradient plans: its own, or the module default."""
+        return self.gradient_rows if self.gradient_rows is not None else gp_state.gradient_rows()
+
     def _plan_for(self, B: int, grad: bool = False):
-        """The forward plan (with gradient buffers when ``grad``), grown (powers of two) to hold B candidates."""
-        cur = self._plan_grad if grad else self._plan
+        """The forward plan (with gradient buffers when ``grad``: the plan of the current gradient-rows mode),
+        grown (powers of two) to hold B candidates."""
+        mode = self._rows_mode() if grad else "staged"
+        cur = self._plans_grad.get(mode) if grad else self._plan
+        if grad:
+            self._plan_grad = cur
         if cur is None or cur.max_B < B:
             cap = 1
             while cap < B:
@@ -441,9 +460,10 @@ class DiscreteKnowledgeGradient(_Base):
                 raise UnsupportedError("precision='fp32' is forward only; use precision='fp64' for gradients")
             if self._target_error is not None:
                 raise self._target_error
-            cur = self._state.plan(self._W, self._target, max(cap, 16), grad=grad, f32=self.precision == "fp32")
+            cur = self._state.plan(self._W, self._target, max(cap, 16), grad=grad, f32=self.precision == "fp32",
+                                   grad_rows=mode)
             if grad:
-                self._plan_grad = cur
+                self._plan_grad = self._plans_grad[mode] = cur
             else:
                 self._plan = cur
         return cur
@@ -486,7 +506,7 @@ class DiscreteKnowledgeGradient(_Base):
             xs = xs.detach().to("cpu", torch.double).contiguous()
         B = xs.numel() // d
         plan = self._plan_grad
-        if plan is None or plan.max_B < B:
+        if plan is None or plan.max_B < B or plan.grad_rows != self._rows_mode():
             plan = self._plan_for(B, grad=True)
         batch = X.shape[:-2] if X.dim() > 2 else X.shape[:-1]
         return plan.forward_grad_host_shaped(xs, B, batch, X.shape)
@@ -494,7 +514,9 @@ class DiscreteKnowledgeGradient(_Base):
     def _targets_plan_for(self, key: tuple, B: int, grad: bool = False):
         """The plan of the targets ``key`` (``normalise_targets``), kept beside ``_plan`` / ``_plan_grad`` by
         (key, grad) and grown as ``_plan_for`` grows them; ``_refresh`` drops these with the other two."""
-        cur = self._plans_targets.get((key, grad))
+        mode = self._rows_mode() if grad else "staged"
+        ckey = (key, grad) if mode == "staged" else (key, grad, mode)
+        cur = self._plans_targets.get(ckey)
         if cur is None or cur.max_B < B:
             cap = 1
             while cap < B:
@@ -502,8 +524,8 @@ class DiscreteKnowledgeGradient(_Base):
             if grad and self.precision == "fp32":
                 raise UnsupportedError("precision='fp32' is forward only; use precision='fp64' for gradients")
             cur = self._state.plan(self._W, None, max(cap, 16), grad=grad, f32=self.precision == "fp32",
-                                   targets=key)
-            self._plans_targets[(key, grad)] = cur
+                                   targets=key, grad_rows=mode)
+            self._plans_targets[ckey] = cur
         return cur
 
     @t_batch_mode_transform(expected_q=1)

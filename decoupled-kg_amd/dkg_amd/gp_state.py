@@ -199,6 +199,33 @@ def incremental_state() -> bool:
     return _INCREMENTAL
 
 
+_GRADIENT_ROWS = "staged"
+GRADIENT_ROWS_MODES = ("staged", "auto", "global")
+
+
+def check_gradient_rows(mode) -> str:
+    if mode not in GRADIENT_ROWS_MODES:
+        raise ValueError(f"gradient rows mode must be one of {GRADIENT_ROWS_MODES}, got {mode!r}")
+    return mode
+
+
+def set_gradient_rows(mode: str) -> str:
+    """Where the gradient plans of ``DiscreteKnowledgeGradient`` (``forward`` with autograd,
+    ``value_and_grad_host``, ``forward_targets``, ``value_and_grad_host_targets``, and with them
+    ``optimize_acqf``, ``run_mobo`` and ``run_smoke``) take the candidates' Q_X and J rows from, for every
+    acquisition built without ``gradient_rows``: ``"staged"`` (the default: LDS, ``UnsupportedError`` where
+    they do not fit), ``"auto"`` (the same plans, and global rows where ``"staged"`` refuses) or ``"global"``
+    (global rows always; a test hook).  See ``ForwardPlan``.  Returns the previous mode."""
+    global _GRADIENT_ROWS
+    prev = _GRADIENT_ROWS
+    _GRADIENT_ROWS = check_gradient_rows(mode)
+    return prev
+
+
+def gradient_rows() -> str:
+    return _GRADIENT_ROWS
+
+
 def state_stats() -> dict:
     """How the shared device states were made since the last reset: ``full_builds`` (a whole
     ``DeviceGPState``), ``appends`` (rows appended) and ``append_fallbacks`` (an append that was not positive
@@ -293,13 +320,19 @@ class DeviceGPState:
         return st
 
     def plan(self, W: torch.Tensor, target, max_B: int, grad: bool = False, force_walk: bool = False,
-             f32: bool = False, fused: bool = False, no_chain: bool = False, targets=None) -> "ForwardPlan":
-        return ForwardPlan(self, W, target, max_B, grad, force_walk, f32, fused, no_chain, targets=targets)
+             f32: bool = False, fused: bool = False, no_chain: bool = False, targets=None,
+             grad_rows: str = "staged") -> "ForwardPlan":
+        return ForwardPlan(self, W, target, max_B, grad, force_walk, f32, fused, no_chain, targets=targets,
+                           grad_rows=grad_rows)
 
     def forward(self, X: torch.Tensor, W: torch.Tensor, target, kg_pairs=None, timed: bool = False):
         """One-shot forward (builds a plan on the fly); see ForwardPlan for the fast path."""
         p = ForwardPlan(self, W, target, max(1, X.shape[0]))
         return p.forward(X, kg_pairs=kg_pairs, timed=timed)
+
+
+# ForwardPlan(grad_rows=...): the plan flag of each mode
+GRAD_ROWS_FLAGS = {"staged": 0, "auto": _lib.DKG_PLAN_GRAD_GLOBAL_ROWS, "global": _lib.DKG_PLAN_FORCE_GLOBAL_ROWS}
 
 
 class ForwardPlan:
@@ -316,11 +349,21 @@ class ForwardPlan:
     envelope once per (target, candidate), and ``forward`` / ``forward_into`` / ``forward_grad`` /
     ``forward_grad_host`` / ``forward_host`` / ``forward_stats`` return tensors with a leading T axis, row
     tau bit for bit what a single-target plan of ``targets[tau]`` returns.  Not with ``fused`` or
-    ``forward_batches_into`` (``UnsupportedError``); ``lines`` exports the lines of ``targets[0]``."""
+    ``forward_batches_into`` (``UnsupportedError``); ``lines`` exports the lines of ``targets[0]``.
+
+    ``grad_rows`` (gradient plans; ignored without ``grad``): where the envelope takes the candidates' Q_X and J
+    rows from.  ``"staged"``: LDS, and ``UnsupportedError`` for a model whose rows do not fit there.
+    ``"auto"`` (``DKG_PLAN_GRAD_GLOBAL_ROWS``): the same plan wherever ``"staged"`` builds one, and where it
+    refuses for the rows a streaming plan that reads them from the workspace.  ``"global"``
+    (``DKG_PLAN_FORCE_GLOBAL_ROWS``, a test hook): that streaming plan on any shape.  ``grad_rows_global``
+    tells which the plan runs."""
 
     def __init__(self, state: DeviceGPState, W: torch.Tensor, target, max_B: int, grad: bool = False,
                  force_walk: bool = False, f32: bool = False, fused: bool = False, no_chain: bool = False,
-                 targets=None):
+                 targets=None, grad_rows: str = "staged"):
+        if grad_rows not in GRAD_ROWS_FLAGS:
+            raise ValueError(f"grad_rows must be one of {GRADIENT_ROWS_MODES}, got {grad_rows!r}")
+        self.grad_rows = grad_rows
         lib = _lib.load()
         self.state = state
         self.device = state.device
@@ -353,7 +396,7 @@ class ForwardPlan:
         self.f32 = bool(f32)
         flags = ((_lib.DKG_PLAN_GRAD if self.grad else 0) | (_lib.DKG_PLAN_FORCE_WALK if force_walk else 0)
                  | (_lib.DKG_PLAN_F32 if self.f32 else 0) | (_lib.DKG_PLAN_FUSED if fused else 0)
-                 | (_lib.DKG_PLAN_NO_CHAIN if no_chain else 0))
+                 | (_lib.DKG_PLAN_NO_CHAIN if no_chain else 0) | (GRAD_ROWS_FLAGS[grad_rows] if self.grad else 0))
         nbytes = lib.dkg_plan_bytes()
         self.host = ctypes.create_string_buffer(nbytes)
         if self.targets is not None:
@@ -376,6 +419,7 @@ class ForwardPlan:
                                          self.ws.numel(), self.host, _lib.ptr(self.dev),
                                          current_stream_ptr(self.device)), "dkg_plan_init")
         self.fused = bool(lib.dkg_plan_fused(self.host))  # forward_into is one fused launch
+        self.grad_rows_global = bool(lib.dkg_plan_grad_rows_of(self.host))  # the envelope reads global rows
         self._fwd = lib.dkg_plan_forward
         self._fwd_batches = lib.dkg_plan_forward_batches
         self._fwd_timed = lib.dkg_plan_forward_timed

@@ -238,6 +238,10 @@ class DiscreteKgOptimisationSpec:
     ``n_discretisation_points_per_axis``: grid points per axis of the discretisation
     (``make_torch_std_grid``); ``num_restarts`` / ``raw_samples`` / ``batch_limit`` /
     ``max_iter``: passed to ``optimize_acqf`` exactly as the reference does (:217-224).
+
+    The gradient plans of the acquisitions it builds follow the module default of
+    ``dkg_amd.set_gradient_rows`` (no argument here): under ``"staged"`` a model whose gradient rows do not
+    fit in LDS raises ``UnsupportedError``, under ``"auto"`` it is optimised with global rows.
     """
 
     def __init__(self, n_discretisation_points_per_axis: int, num_restarts: int, raw_samples: int,

@@ -337,11 +337,28 @@ int dkg_forward_timed(const dkg_output* outs, int m, int d, const double* disc, 
  * filters without its sample chain: the extremes from the streamed lines, the quickhull refinement and
  * the walks of the list-overflow path for every pair; same results, slower. */
 #define DKG_PLAN_NO_CHAIN 16
+/* DKG_PLAN_GRAD_GLOBAL_ROWS (with DKG_PLAN_GRAD only; DKG_ERR_ARG without it): where the gradient plan would be
+ * refused because every output's Q_X row and its d rows of J do not fit in the envelope stage's LDS
+ * ("gradient: ... exceed the envelope stage's LDS"), build a streaming plan whose envelope reads those rows
+ * from the workspace instead ("global rows").  Every plan that is built without the flag is built the same,
+ * bit for bit, with it; the other refusals are unchanged. */
+#define DKG_PLAN_GRAD_GLOBAL_ROWS 32
+/* DKG_PLAN_FORCE_GLOBAL_ROWS (test hook, with DKG_PLAN_GRAD only): the streaming global-rows envelope on any
+ * shape; the bits of the plan's staged-rows streaming envelope. */
+#define DKG_PLAN_FORCE_GLOBAL_ROWS 128
 size_t dkg_plan_bytes(void);
 size_t dkg_plan_workspace(const dkg_output* outs, int m, int d, int N, int max_B, int S, int flags);
 int dkg_plan_init(const dkg_output* outs, int m, int d, const double* disc, int N, const double* weights, int S,
                   int target, int max_B, int flags, void* workspace, size_t workspace_bytes, void* host_plan,
                   void* dev_plan, void* stream);
+/* Where a gradient plan of these outputs, N discretisation points, S scalarisations and `flags` (with
+ * DKG_PLAN_GRAD) takes the candidates' Q_X and J rows from: 0 staged in LDS, 1 global rows
+ * (DKG_PLAN_GRAD_GLOBAL_ROWS where the staged rows do not fit, DKG_PLAN_FORCE_GLOBAL_ROWS always), or the
+ * status dkg_plan_init would refuse the shape or the flags with, negated (-DKG_ERR_*; dkg_last_error set).  Host
+ * arithmetic only: no device call, and the outputs' pointers are checked for NULL, never followed. */
+int dkg_plan_grad_rows(const dkg_output* outs, int m, int d, int N, int S, int flags);
+/* 1 if the plan's gradient envelope reads global rows, 0 if it stages them (or the plan has no gradient). */
+int dkg_plan_grad_rows_of(const void* host_plan);
 /* A plan of T targets: `targets` (host, [T]) holds 1 <= T <= m + 1 distinct entries in [-1, m), -1 = all
  * outputs observed; anything else is DKG_ERR_ARG.  The cross and covariance stages do not depend on the
  * target, so every call on the plan runs them once and the envelope once per (target, candidate): row
