@@ -446,6 +446,13 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
   return __hiloint2double(hi, lo);
 }
 
+// Lane `l`'s value of v, l per lane in 0..63 (ds_bpermute of both halves; full EXEC).
+__device__ __forceinline__ double gather_f64(double v, int l) {
+  const int lo = __builtin_amdgcn_ds_bpermute(l << 2, __double2loint(v));
+  const int hi = __builtin_amdgcn_ds_bpermute(l << 2, __double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+
 __device__ __forceinline__ int lanes_below(uint64_t mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
 }

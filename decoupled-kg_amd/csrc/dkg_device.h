@@ -605,8 +605,11 @@ __device__ __forceinline__ EdgeSum env_pair_regs_edges(Build&& build, int nl, in
       double la[MAXL], lb[MAXL];
       build(la, lb);
       const double bT = sgpr_f64(f.bT);
-      int n = env_compact<MAXL, ENV_CAP>(la, lb, HalfChords{{c.s[0], c.k[0], c.s[1], c.k[1]}, bT, false}, lane, sb,
-                                         sa, si);
+      // T = L (the top line has the smallest slope): L - V1 and V1 - T have db = 0 and keep nothing, so the lower
+      // half would drop T itself (slope bT) and the walk would find no L in the list; T lies on T - V2
+      const bool tl = uniform(!(f.bT > f.bL));
+      const HalfChords lower{{tl ? c.s[2] : c.s[0], tl ? c.k[2] : c.k[0], c.s[1], c.k[1]}, bT, false};
+      int n = env_compact<MAXL, ENV_CAP>(la, lb, lower, lane, sb, sa, si);
       n = env_compact<MAXL, ENV_CAP>(la, lb, HalfChords{{c.s[2], c.k[2], c.s[3], c.k[3]}, bT, true}, lane, sb, sa,
                                      si, n);
       f.cnt = n;

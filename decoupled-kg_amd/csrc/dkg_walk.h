@@ -252,7 +252,7 @@ __device__ __forceinline__ EdgeSum walk_list(int nc, int lane, const double* sb,
 // steps, :382-401, each step's argmin being exactly the row's).  A row whose
 // minimum is attained by several lanes (concurrent lines, duplicates) is
 // resolved by the full key over those lanes (wave_walk_min).  The KG edge
-// terms are left on the winning lanes (EdgeSum, evaluated by finish_edges);
+// terms are left one per lane in walk order (EdgeSum, evaluated by finish_edges);
 // *cmax = 0 when every breakpoint is within WALK_XGUARD, else the largest
 // |breakpoint|.
 template <int R>
@@ -306,7 +306,7 @@ __device__ __forceinline__ EdgeSum walk_table(int nc, int lane, const double* sb
   int cur = (int)__builtin_ctzll(lead) / G;
   if (out && lane == 0 && out->cap > 0) out->idx[0] = si[cur];
   uint64_t win = 0;
-  int h = 0;
+  int h = 0, src = lane;  // lane s: the winning lane of step s
   constexpr uint64_t ROW = (G == 64) ? ~0ull : ((1ull << G) - 1);
   for (int guard = 0; guard < nc; ++guard) {
     const uint64_t rm = hits & (ROW << (cur * G));
@@ -319,6 +319,7 @@ __device__ __forceinline__ EdgeSum walk_table(int nc, int lane, const double* sb
       w = (int)__builtin_ctzll(ballot(sel && kb == p.k));
     }
     win |= 1ull << w;
+    src = (lane == h) ? w : src;
     if (out && h + 1 < out->cap) {
       const int kw = __builtin_amdgcn_readlane(kb, w);
       const double xw = readlane_f64(xb, w);
@@ -333,7 +334,10 @@ __device__ __forceinline__ EdgeSum walk_table(int nc, int lane, const double* sb
   const bool won = (win >> lane) & 1;
   *nhull = h + 1;
   *cmax = (ballot(won && !(fabs(xb) <= WALK_XGUARD)) != 0) ? wave_max(won ? fabs(xb) : 0.0) : 0.0;
-  return {0.0, (bb <= bT) ? -xb : xb, bb - bi, won};
+  // The edge of step s moves from its winning lane (a list position) to lane s, where the step-by-step walks
+  // leave it (WalkAcc): the wave sum then adds the terms in envelope order, so KG_w is a function of the
+  // envelope alone, the same bits for any order or superset of the list and for walk_list / walk_regs.
+  return {0.0, gather_f64((bb <= bT) ? -xb : xb, src), gather_f64(bb - bi, src), lane < h};
 }
 
 // Walk over the candidate list: the successor table up to 32 entries, the

@@ -251,6 +251,191 @@ def grad_row_problem(row, B=None):
                      row["seed"], **row["kw"])
 
 
+# The forward case matrix (tests/test_gpu_forward_matrix.py on the device, tests/test_forward_matrix_oracle.py on
+# the reference alone): the production forward (no kg_pairs: env_flat, the plan's top hint, env_top + env_span)
+# in every output bucket M = 1, 2, 3, 4, 8 (m = 5 padded, and m = 8) times every envelope instantiation of
+# launch_env_bucket<M, false>: 2 / 8 / 17 / 33 register slots and the streaming kernel.  N only lands the row in
+# its bucket; n <= 64 per output, all different; d cycles over 2, 3, 4; the kernel families cycle over
+# ALL_FAMILIES from another start in every column, so the M = 1 rows do not all run Matern-5/2; S = 8, B = 19,
+# targets (None, m - 1).  Seeds are chosen on the oracle alone (test_forward_matrix_oracle.py states the
+# conditions).  GRAD_MATRIX rows are reused where their shape is the cell's (M3-mixed, M4, M8-padded-m5, M8-full).
+#
+# The M = 8 bucket has no 33-slot forward: two staged record arrays of 64 * 33 * 8 doubles are 264 KiB, over the
+# envelope's 160 KiB of LDS at any N, so every M = 8 plan with N + 1 > 1088 streams.  The cell is kept as the rows
+# "M8p-N1100" / "M8f-N1100" (the N of the other buckets' 33-slot rows), which assert the streaming kernel there.
+FORWARD_NS = {"M1": (37,), "M2": (40, 33), "M3": (37, 50, 23), "M4": (33, 48, 17, 64),
+              "M8p": (20, 31, 16, 45, 27), "M8f": (20, 31, 16, 45, 27, 38, 18, 52)}
+FORWARD_GEOMETRIES = (("slots2", 100, 2, 0), ("slots8", 200, 8, 0), ("slots17", 600, 17, 0),
+                      ("slots33", 1100, 33, 0), ("stream", 2200, 0, 1))
+FORWARD_REUSED = {("M3", "slots8"): "M3-mixed", ("M4", "slots8"): "M4", ("M8p", "slots2"): "M8-padded-m5",
+                  ("M8f", "slots2"): "M8-full"}
+# (seed, grad_case overrides) picked on the oracle so that every bucket has a staged row with at least 8 flat pairs
+# (env_flat) next to at least 8 walked pairs with KG > 0 (test_forward_matrix_oracle.py); elsewhere the seed is
+# 300 + 10 * bucket + column.  noise = 1e-3 for every output (the default is 1e-2 (1 + i)) shrinks the candidate's
+# posterior deviation, which is line 0's slope: what a pair needs to be flat.  With target None that takes every
+# output's deviation small at once: 8 such pairs at M = 1 (one candidate, all flat) and M = 2, at most 2 in the
+# larger buckets over the few hundred seeds tried per row, whose flat pairs are the target m - 1 ones.
+FORWARD_PICKS = {"M1-slots2": (49, {}), "M2-slots17": (8, dict(noise=1e-3)), "M3-slots17": (13, dict(noise=1e-3)),
+                 "M4-slots2": (3, dict(noise=1e-3)), "M8p-slots8": (120, {}), "M8f-slots8": (23, dict(noise=1e-3))}
+
+
+def _forward_matrix():
+    rows = []
+    for bi, (mk, ns) in enumerate(FORWARD_NS.items()):
+        m = len(ns)
+        for gi, (gk, N, slots, stream) in enumerate(FORWARD_GEOMETRIES):
+            reused = FORWARD_REUSED.get((mk, gk))
+            if reused is not None:
+                row = dict(GRAD_ROWS[reused], targets=(None, m - 1), cell=(mk, gk))
+            else:
+                rid = f"{mk}-{gk}"
+                if m > 4 and gk == "slots33":  # no 33-slot kernel in the M = 8 bucket: streams by its LDS
+                    rid, slots, stream = f"{mk}-N1100", 0, 1
+                fam = ALL_FAMILIES[gi % 4:] + ALL_FAMILIES[:gi % 4]
+                seed, kw = FORWARD_PICKS.get(rid, (300 + 10 * bi + gi, {}))
+                row = _row(rid, m, 2 + (bi + gi) % 3, ns, fam, N, 8, 19, (None, m - 1), slots, stream=stream,
+                           seed=seed, **kw)
+                row["cell"] = (mk, gk)
+            rows.append(row)
+    # three and five workgroups per candidate (S = 24, 40) in the M = 3 and M = 4 buckets
+    rows.append(dict(_row("M3-S24", 3, 3, FORWARD_NS["M3"], ALL_FAMILIES, 200, 24, 19, (None, 2), 8, split=3,
+                          seed=371), cell=("M3", "split3")))
+    rows.append(dict(_row("M4-S40", 4, 2, FORWARD_NS["M4"], ALL_FAMILIES, 600, 40, 19, (None, 3), 17, split=5,
+                          seed=372), cell=("M4", "split5")))
+    return rows
+
+
+FORWARD_MATRIX = _forward_matrix()
+FORWARD_ROWS = {r["id"]: r for r in FORWARD_MATRIX}
+FORWARD_CASES = [(r["id"], t) for r in FORWARD_MATRIX for t in r["targets"]]
+
+# streaming forwards over lists longer than LIST_CAP_STREAM = 512 (d = 1 grids in the long-M12 style): M = 1 takes
+# the older streaming path (env_extremes_stream / refine_stream / walk_stream), M = 2 the staged chain and then
+# its overflow.  N is the smallest tried at which some pair's envelope exceeds 512 lines on the oracle.
+FORWARD_LONG = [
+    _row("long-stream-m1", 1, 1, (6,), ("M12",), 2600, 3, 9, (None,), 0, stream=1, seed=81, lengthscale=1.0,
+         noise=0.1, grid=True, mean_shift=1.2),
+    _row("long-stream-m2", 2, 1, (6, 6), ("M12",), 3000, 3, 9, (None,), 0, stream=1, seed=3, lengthscale=1.0,
+         noise=0.1, grid=True),
+]
+FORWARD_LONG_ROWS = {r["id"]: r for r in FORWARD_LONG}
+
+HINT_STATES = ("line0", "grid-unique", "grid-tied", "equal")
+
+
+def forward_classes(a, b, pairs=None):
+    """Which branches of the production forward a set of oracle lines [B, S, L] (line 0: the candidate) asks for,
+    per (candidate, scalarisation) pair.  A classifier of inputs, not a tolerance.  -> dict of [B, S] tensors:
+
+      state   : index into HINT_STATES, the plan's top hint (dkg_device.h envelope_body): with a0 line 0's
+                intercept, A1 the largest intercept of lines k >= 1 and c1 how many of them attain it:
+                a0 > A1 (line 0 is T), a0 < A1 with c1 == 1 (that grid line is T), a0 < A1 with c1 > 1 (tied: no
+                hint, env_top finds T) and a0 == A1 (no hint);
+      flat    : env_flat's predicate restated: with T = (max a, ties: min b), every line that is not an exact
+                copy of T has fma(48, |b - b_T|, a - a_T) <= 2^-40 (a - a_T) (the sign as the kernel has it:
+                a - a_T <= 0), so the pair's KG is exactly 0 and the kernel does not walk it;
+      kg_zero : the reference KG of the pair is exactly 0.0 (``pairs``: the oracle's kg_pairs_from_lines of the
+                same lines when the caller has them already)."""
+    from oracle.discretekg import kg_pairs_from_lines
+
+    a0 = a[..., 0]
+    A1 = a[..., 1:].amax(-1)
+    c1 = (a[..., 1:] == A1[..., None]).sum(-1)
+    state = torch.where(a0 > A1, 0, torch.where(a0 == A1, 3, torch.where(c1 == 1, 1, 2)))
+    aT = a.amax(-1, keepdim=True)
+    bT = torch.where(a == aT, b, torch.inf).amin(-1, keepdim=True)
+    da = a - aT
+    # the kernel's two fmas written as products and sums: two more roundings of 2^-53 (|da| + 48 |b - bT|), which
+    # can move only a pair within 2^-51 |da| of a boundary that itself stands 2^-40 |da| inside the true one
+    v = 48.0 * (b - bT).abs() + da
+    worst = torch.where((a == aT) & (b == bT), -torch.inf, v - 2.0 ** -40 * da).amax(-1)
+    flat = worst <= 0.0
+    if pairs is None:
+        pairs = kg_pairs_from_lines(a, b)
+    return {"state": state, "flat": flat, "kg_zero": pairs == 0.0}
+
+
+def forward_row_problem(row, B=None):
+    """grad_case of a FORWARD_MATRIX / FORWARD_LONG row."""
+    return grad_row_problem(row, B)
+
+
+# Inputs for the states of the plan's top hint no matrix row reaches in numbers (every row is almost all
+# "grid-unique"): per output bucket and slot count, a grad_case base (S = 8, B = 19; N lands the slot bucket and is
+# small enough for line 0 to beat every grid intercept now and then: the chance falls with N, so the M = 8
+# bucket's 17-slot case takes the smallest N of that bucket) and three edits of it (hint_case).
+HINT_NS = {k: FORWARD_NS[k] for k in ("M1", "M3", "M4", "M8p")}
+HINT_N = {2: 40, 8: 300, 17: 700}
+HINT_KINDS = ("line0", "tied", "equal", "equal-tied")
+HINT_POOL = 2000
+# seeds (the default is 500 + 10 * bucket + slots) moved until the pool holds at least 8 pairs with a0 > A1
+HINT_SEEDS = {("M1", 8): 1, ("M1", 17): 3, ("M4", 17): 1}
+
+
+def _top_rows(om, X, D, W):
+    """Per scalarisation, the row of D whose line has the largest intercept (the oracle's; target-independent)."""
+    from oracle.discretekg import lines_batched
+
+    return lines_batched(om, X[:1], D, W, None)[0][0, :, 1:].argmax(-1)
+
+
+def hint_case(mk, slots, kind):
+    """-> (ModelListGPState, D, W, X [19, d]) whose oracle lines reach a state of the top hint:
+
+      line0      : the 10 candidates of a pool of HINT_POOL uniform ones with the most scalarisations in which
+                   line 0's intercept exceeds every grid line's (a0 > A1), and the 9 with the fewest;
+      tied       : D with the argmax-intercept rows of scalarisations 0..3 appended again: their top grid
+                   intercept is attained twice (c1 = 2), so the plan gives no hint there;
+      equal      : candidates 0 and 1 placed on the argmax rows of scalarisations 0 and 1: line 0 is an exact copy
+                   of the top grid line (a0 == A1);
+      equal-tied : both edits."""
+    from oracle.discretekg import lines_batched
+
+    m = len(HINT_NS[mk])
+    bi = list(FORWARD_NS).index(mk)
+    N = 512 if (mk, slots) == ("M8p", 17) else HINT_N[slots]
+    args = (m, 2 + (bi + slots) % 3, HINT_NS[mk], ALL_FAMILIES, N, 8)
+    seed = HINT_SEEDS.get((mk, slots), 500 + 10 * bi + slots)
+    state, D, W, X = grad_case(*args, 19, seed)
+    om = to_oracle(state)
+    if kind == "line0":
+        pool = grad_case(*args, HINT_POOL, seed)[3]
+        a0 = lines_batched(om, pool, D[:1], W, None)[0][..., 0]                   # [pool, S]
+        A1 = lines_batched(om, pool[:1], D, W, None)[0][0, :, 1:].amax(-1)        # [S]
+        order = torch.sort((a0 > A1).sum(-1), descending=True, stable=True).indices
+        return state, D, W, torch.cat([pool[order[:10]], pool[order[-9:]]])
+    top = _top_rows(om, X, D, W)
+    if kind in ("equal", "equal-tied"):
+        X = X.clone()
+        X[0], X[1] = D[top[0]], D[top[1]]
+    if kind in ("tied", "equal-tied"):
+        D = torch.cat([D, D[torch.unique(top[:4])]])
+    return state, D, W, X
+
+
+def assert_envelopes_are_reference_walk(a, b, hull):
+    """On lines a, b [B, S, L] a plan built (device tensors, exported bit for bit by dkg_plan_lines): the device
+    walk (calculate_epigraph_indices_batched) returns the oracle walk's indices and intersections exactly, and the
+    forward's envelope sizes ``hull`` [B, S] (dkg_plan_hull_sizes) equal the walk's -- every (candidate,
+    scalarisation) pair.  -> the envelope sizes, sorted."""
+    from dkg_amd import calculate_epigraph_indices_batched
+    from oracle.discretekg import calculate_epigraph_indices as ref_epigraph
+
+    B, S, L = a.shape
+    idx, xs, cnt = calculate_epigraph_indices_batched(a, b)
+    ac, bc, idx, xs, cnt, hull = a.cpu(), b.cpu(), idx.cpu(), xs.cpu(), cnt.cpu(), hull.cpu()
+    sizes = []
+    for i in range(B):
+        for j in range(S):
+            ri, rx = ref_epigraph(ac[i, j], bc[i, j])
+            m = len(ri)
+            assert int(cnt[i, j]) == m and int(hull[i, j]) == m, (i, j, int(cnt[i, j]), int(hull[i, j]), m)
+            assert torch.equal(idx[i, j, :m], ri), (i, j)
+            assert torch.equal(xs[i, j, : m - 1], rx), (i, j)
+            sizes.append(m)
+    return sorted(sizes)
+
+
 def oracle_value_and_grad(om, X, D, W, target):
     """KG [B] and dKG/dX [B, d] of the batched oracle by torch.autograd."""
     from oracle.discretekg import discrete_kg_batched

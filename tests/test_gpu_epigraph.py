@@ -21,7 +21,7 @@ import re
 import pytest
 import torch
 
-from helpers import to_oracle
+from helpers import assert_envelopes_are_reference_walk, to_oracle
 from oracle.discretekg import calculate_epigraph_indices as ref_epigraph
 from oracle.discretekg import calculate_expected_value_of_piecewise_linear_function as ref_expectation
 
@@ -299,16 +299,5 @@ def test_forward_envelopes_are_the_reference_walk(workload, nX, target):
     """On the lines the plan builds (exported bit for bit by dkg_plan_lines): the device walk returns
     the oracle walk's indices and intersections exactly, and the forward's envelope sizes
     (dkg_plan_hull_sizes) equal the walk's -- every (candidate, scalarisation) pair."""
-    from dkg_amd import calculate_epigraph_indices_batched
-
     a, b, pairs, hull = _plan_lines(workload, nX, target)
-    B, S, L = a.shape
-    idx, xs, cnt = calculate_epigraph_indices_batched(a, b)
-    ac, bc, idx, xs, cnt, hull = a.cpu(), b.cpu(), idx.cpu(), xs.cpu(), cnt.cpu(), hull.cpu()
-    for i in range(B):
-        for j in range(S):
-            ri, rx = ref_epigraph(ac[i, j], bc[i, j])
-            m = len(ri)
-            assert int(cnt[i, j]) == m and int(hull[i, j]) == m, (i, j, int(cnt[i, j]), int(hull[i, j]), m)
-            assert torch.equal(idx[i, j, :m], ri), (i, j)
-            assert torch.equal(xs[i, j, : m - 1], rx), (i, j)
+    assert_envelopes_are_reference_walk(a, b, hull)
