@@ -13,12 +13,15 @@
 //                           are the largest key below and the smallest key above its own), and the survivor order
 //                           by counting the keys (rank, -crowding, index) below a point's own.  Every loop is
 //                           bounded by Q; phases meet at __syncthreads.
+//   pareto_clear / dom / peel / crowd / order kernels: the same results for up to 16384 points from the caller's
+//                           workspace, the per-point scans spread over the device (the wide path, below).
 //   pareto_variation_kernel binary tournament, bounded simulated binary crossover (Deb & Agrawal 1995) and bounded
 //                           polynomial mutation (Deb et al. 2002), one thread per (pair of children, coordinate),
 //                           every random number read from the caller's uniforms (layout: include/dkg.h).
 //   pareto_init / normalise / gather: the glue of dkg_pareto_nsga2.
 // The three stages' arithmetic is compiled without FP contraction where a host restatement must give the same bits
 // (crowding) or nearly so (variation).
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 
@@ -292,6 +295,279 @@ static hipError_t launch_rank(const double* F, int Q, int m, int keep, int* rank
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The wide path: the same ranks, crowding distances and order for Q <= 16384 points, the per-point work spread
+// over the device.  Five stream-ordered launches, no workgroup waits on another:
+//   pareto_clear_kernel   cnt = 0, rk = -2, order = -1, the scalars (every call: the workspace carries no state)
+//   pareto_dom_kernel     grid (point tiles, k slices): a thread holds its point's row in registers, the slice's
+//                         rows are LDS broadcasts, the partial dominator count goes to cnt[i] by an integer
+//                         atomicAdd (an integer sum does not depend on the arrival order)
+//   pareto_peel_kernel    one workgroup, the only sequential part: fronts from cnt until `keep` points are ranked
+//   pareto_crowd_kernel   one wave per point: a front's min / max and a member's neighbours in (f_j, index) order
+//                         are selections of input values, so the wave reduction gives the one-workgroup kernel's
+//                         values; then its arithmetic
+//   pareto_order_kernel   one wave per point: an integer wave sum of the keys below its own
+// Scratch (the caller's workspace): cnt [Q], rk [Q] ints, 64 scalars' room.
+constexpr int WR_MAXQ = 16384;
+constexpr int PD_TILE = 256;   // points per workgroup of pareto_dom_kernel, one per thread
+constexpr int PD_SLICE = 128;  // rows k per workgroup: Q = 2000 gives 8 x 16 workgroups
+constexpr int WR_WAVES = 4;    // waves (points) per workgroup of the crowding and order kernels
+constexpr size_t WR_LDS = 160 * 1024;
+
+struct WideWs {
+  size_t cnt, rk, scalars, total;
+};
+__host__ inline WideWs wide_ws(int Q) {
+  WideWs w{};
+  const size_t q = ((size_t)Q * sizeof(int) + 255) & ~(size_t)255;
+  w.cnt = 0;
+  w.rk = q;
+  w.scalars = 2 * q;
+  w.total = 2 * q + 256;
+  return w;
+}
+
+// pareto_peel_kernel's LDS: the unranked dominator counts [Q], the front's member list [Q], two counters, and
+// F [Q][m] where it fits beside them
+__host__ __device__ inline size_t peel_list_bytes(int Q) {
+  return (2 * (size_t)Q * sizeof(int) + 16 + 15) & ~(size_t)15;
+}
+__host__ __device__ inline bool peel_f_in_lds(int Q, int m) {
+  return peel_list_bytes(Q) + (size_t)Q * m * sizeof(double) <= WR_LDS;
+}
+
+__global__ __launch_bounds__(256) void pareto_clear_kernel(int Q, int* __restrict__ cnt, int* __restrict__ rk,
+                                                           int* __restrict__ scalars, int* __restrict__ order) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < Q) {
+    cnt[i] = 0;
+    rk[i] = -2;
+    order[i] = -1;
+  }
+  if (i < 64) scalars[i] = 0;
+}
+
+template <int MB>
+__global__ __launch_bounds__(PD_TILE) void pareto_dom_kernel(const double* __restrict__ F, int Q, int m,
+                                                             int* __restrict__ cnt) {
+  __shared__ __attribute__((aligned(16))) double rows[PD_SLICE * MB];  // the slice's rows, padded to MB as load_row
+  const int tid = threadIdx.x;
+  const int k0 = blockIdx.y * PD_SLICE, kn = min(PD_SLICE, Q - k0);
+  for (int e = tid; e < kn * MB; e += PD_TILE) rows[e] = F[(size_t)(k0 + e / MB) * m + min(e % MB, m - 1)];
+  __syncthreads();
+  const int i = blockIdx.x * PD_TILE + tid;
+  double own[MB];  // a thread past Q holds row Q - 1 and writes nothing
+  load_row<MB>(F, min(i, Q - 1), m, own);
+  int c = 0;
+#pragma unroll 4
+  for (int k = 0; k < kn; ++k) {
+    double fk[MB];
+#pragma unroll
+    for (int j = 0; j < MB; ++j) fk[j] = rows[k * MB + j];
+    c += dominates<MB>(fk, own) ? 1 : 0;
+  }
+  if (i < Q && c) atomicAdd(&cnt[i], c);
+}
+
+// One workgroup; thread t owns the points t, t + nt, ... (16 of them at Q = 16384), their unranked dominator
+// counts in LDS: > 0 dominated, 0 a member of the next front, -1 ranked.  Per round: the members list
+// themselves, `done >= keep` is tested, and only when the peel goes on are the members' dominations taken off
+// the unranked counts (with keep = P of 2P points and a first front of >= P members the peel is one round with no
+// scan).  LDSF: F is staged in LDS; otherwise its rows are read from global memory (<= 1 MiB, L2 resident).
+template <int MB, bool LDSF>
+__global__ __launch_bounds__(1024) void pareto_peel_kernel(const double* __restrict__ F, int Q, int m, int keep,
+                                                           const int* __restrict__ cnt0, int* __restrict__ rk,
+                                                           int* __restrict__ scalars) {
+  extern __shared__ __attribute__((aligned(16))) double pp_smem[];
+  int* cnt = reinterpret_cast<int*>(pp_smem);  // [Q]
+  int* list = cnt + Q;                         // [Q] members of the front being peeled
+  int* nmem = list + Q;                        // [2] members of the front of an even / odd round
+  const double* f = F;
+  const int tid = threadIdx.x, nt = blockDim.x;
+  if constexpr (LDSF) {
+    double* fs = reinterpret_cast<double*>(reinterpret_cast<char*>(pp_smem) + peel_list_bytes(Q));
+    for (int e = tid; e < Q * m; e += nt) fs[e] = F[e];
+    f = fs;
+  }
+  if (tid < 2) nmem[tid] = 0;
+  for (int i = tid; i < Q; i += nt) cnt[i] = cnt0[i];
+  __syncthreads();
+  int done = 0, fronts = 0;
+  for (int r = 0; r < Q; ++r) {
+    int* mine = nmem + (r & 1);
+    for (int i = tid; i < Q; i += nt)
+      if (cnt[i] == 0) list[atomicAdd(mine, 1)] = i;  // any order: only counted over
+    __syncthreads();
+    const int nf = *mine;
+    if (tid == 0) nmem[(r + 1) & 1] = 0;  // last read before the previous round's closing barrier
+    done += nf;
+    fronts += nf > 0 ? 1 : 0;
+    const bool last = done >= keep || nf == 0;  // uniform
+    for (int i = tid; i < Q; i += nt) {
+      const int ci = cnt[i];  // the thread's own points: no other thread reads or writes them
+      if (ci == 0) {
+        rk[i] = r;
+        cnt[i] = -1;
+      } else if (ci > 0 && !last) {
+        double own[MB];
+        load_row<MB>(f, i, m, own);
+        int c = 0;
+#pragma unroll 4
+        for (int q = 0; q < nf; ++q) {
+          double fk[MB];
+          load_row<MB>(f, list[q], m, fk);
+          c += dominates<MB>(fk, own) ? 1 : 0;
+        }
+        cnt[i] = ci - c;
+      }
+    }
+    if (last) break;
+    __syncthreads();  // the list is free for the next round
+  }
+  if (tid == 0) {
+    scalars[0] = fronts;
+    scalars[1] = done;
+  }
+}
+
+__global__ __launch_bounds__(WR_WAVES* WAVE) void pareto_crowd_kernel(const double* __restrict__ F, int Q, int m,
+                                                                      const int* __restrict__ rk,
+                                                                      int* __restrict__ rank,
+                                                                      double* __restrict__ crowd) {
+#pragma clang fp contract(off)
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * WR_WAVES + (threadIdx.x >> 6);
+  if (i >= Q) return;  // wave-uniform, as every branch below
+  const int ri = rk[i];
+  if (ri < 0) {
+    if (lane == 0) {
+      rank[i] = -1;
+      crowd[i] = 0.0;
+    }
+    return;
+  }
+  double cd = 0.0;
+  for (int j = 0; j < m; ++j) {
+    const double fi = F[(size_t)i * m + j];
+    double fmin = fi, fmax = fi, prev = 0.0, next = 0.0;
+    bool hp = false, hn = false;
+#pragma unroll 2
+    for (int k = lane; k < Q; k += WAVE) {
+      const bool in = rk[k] == ri;
+      const double fk = F[(size_t)k * m + j];
+      fmin = (in && fk < fmin) ? fk : fmin;
+      fmax = (in && fk > fmax) ? fk : fmax;
+      const bool before = in && (fk < fi || (fk == fi && k < i));
+      const bool after = in && (fk > fi || (fk == fi && k > i));
+      prev = (before && (!hp || fk > prev)) ? fk : prev;
+      next = (after && (!hn || fk < next)) ? fk : next;
+      hp = hp || before;
+      hn = hn || after;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const double omin = __shfl_xor(fmin, off), omax = __shfl_xor(fmax, off);
+      const double oprev = __shfl_xor(prev, off), onext = __shfl_xor(next, off);
+      const bool ohp = __shfl_xor((int)hp, off) != 0, ohn = __shfl_xor((int)hn, off) != 0;
+      fmin = omin < fmin ? omin : fmin;
+      fmax = omax > fmax ? omax : fmax;
+      prev = (ohp && (!hp || oprev > prev)) ? oprev : prev;
+      next = (ohn && (!hn || onext < next)) ? onext : next;
+      hp = hp || ohp;
+      hn = hn || ohn;
+    }
+    if (!hp || !hn) {
+      cd = cd + __builtin_inf();
+    } else {
+      const double range = fmax - fmin;
+      const double num = next - prev;
+      cd = cd + (range > 0.0 ? num / range : 0.0);
+    }
+  }
+  if (lane == 0) {
+    rank[i] = ri;
+    crowd[i] = cd;
+  }
+}
+
+// order[pos] = i, pos the number of ranked points whose key (rank, -crowding, index) is below i's: < Q whatever
+// the values
+__global__ __launch_bounds__(WR_WAVES* WAVE) void pareto_order_kernel(int Q, const int* __restrict__ rank,
+                                                                      const double* __restrict__ crowd,
+                                                                      int* __restrict__ order) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * WR_WAVES + (threadIdx.x >> 6);
+  if (i >= Q) return;  // wave-uniform
+  const int ri = rank[i];
+  if (ri < 0) return;
+  const double ci = crowd[i];
+  int pos = 0;
+#pragma unroll 2
+  for (int k = lane; k < Q; k += WAVE) {
+    const int rkk = rank[k];
+    const double ck = crowd[k];
+    const bool before = rkk >= 0 && (rkk < ri || (rkk == ri && (ck > ci || (ck == ci && k < i))));
+    pos += before ? 1 : 0;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) pos += __shfl_xor(pos, off);
+  if (lane == 0) order[pos] = i;
+}
+
+static hipError_t launch_rank_wide(const double* F, int Q, int m, int keep, int* rank, double* crowd, int* order,
+                                   void* work, hipStream_t s) {
+  const WideWs w = wide_ws(Q);
+  char* ws = static_cast<char*>(work);
+  int* cnt = reinterpret_cast<int*>(ws + w.cnt);
+  int* rk = reinterpret_cast<int*>(ws + w.rk);
+  int* scalars = reinterpret_cast<int*>(ws + w.scalars);
+  hipError_t e;
+  hipLaunchKernelGGL(pareto_clear_kernel, dim3((std::max(Q, 64) + 255) / 256), dim3(256), 0, s, Q, cnt, rk, scalars,
+                     order);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const dim3 dgrid((Q + PD_TILE - 1) / PD_TILE, (Q + PD_SLICE - 1) / PD_SLICE);
+  if (m <= 2) hipLaunchKernelGGL(pareto_dom_kernel<2>, dgrid, dim3(PD_TILE), 0, s, F, Q, m, cnt);
+  else if (m <= 4) hipLaunchKernelGGL(pareto_dom_kernel<4>, dgrid, dim3(PD_TILE), 0, s, F, Q, m, cnt);
+  else hipLaunchKernelGGL(pareto_dom_kernel<8>, dgrid, dim3(PD_TILE), 0, s, F, Q, m, cnt);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const bool in_lds = peel_f_in_lds(Q, m);
+  const size_t lds = peel_list_bytes(Q) + (in_lds ? (size_t)Q * m * sizeof(double) : 0);
+  const int nt = std::min(1024, (Q + 63) / 64 * 64);
+  auto peel = [&](auto kern) {
+    raise_lds_limit(reinterpret_cast<const void*>(kern), lds);
+    hipLaunchKernelGGL(kern, dim3(1), dim3(nt), lds, s, F, Q, m, keep, (const int*)cnt, rk, scalars);
+  };
+  if (m <= 2) in_lds ? peel(pareto_peel_kernel<2, true>) : peel(pareto_peel_kernel<2, false>);
+  else if (m <= 4) in_lds ? peel(pareto_peel_kernel<4, true>) : peel(pareto_peel_kernel<4, false>);
+  else in_lds ? peel(pareto_peel_kernel<8, true>) : peel(pareto_peel_kernel<8, false>);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const dim3 wgrid((Q + WR_WAVES - 1) / WR_WAVES), wblock(WR_WAVES * WAVE);
+  hipLaunchKernelGGL(pareto_crowd_kernel, wgrid, wblock, 0, s, F, Q, m, (const int*)rk, rank, crowd);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(pareto_order_kernel, wgrid, wblock, 0, s, Q, (const int*)rank, (const double*)crowd, order);
+  return hipGetLastError();
+}
+
+// Which path ranks Q <= 2048 points when the caller gave a workspace: mode -1 the measured rule, 0 never the wide
+// path, 1 always (dkg_debug_pareto_wide).  The rule: the smallest Q of the sweep (tools/bench_pareto.py
+// --rank-sweep; Q = 8 .. 2048, keep = Q / 2, late- and early-generation-like inputs) from which the wide path's
+// median is below the one-workgroup kernel's minimum on both inputs, per objective bucket (DESIGN.md 8c,
+// profiles/pareto_wide/rank_sweep.json): five launches cost 17 - 22 us whatever Q is, the one workgroup 7 - 20 us
+// at Q = 8 and 21 - 66 us at Q = 32.
+static std::atomic<int> g_pareto_wide_mode{-1};
+static int wide_min_q(int m) { return m <= 4 ? 32 : 16; }
+static bool rank_goes_wide(int Q, int m, const void* work) {
+  if (!work) return false;
+  if (Q > PR_MAXQ) return true;
+  const int mode = g_pareto_wide_mode.load(std::memory_order_relaxed);
+  return mode == 1 || (mode < 0 && Q >= wide_min_q(m));
+}
+static hipError_t launch_rank_any(const double* F, int Q, int m, int keep, int* rank, double* crowd, int* order,
+                                  void* work, hipStream_t s) {
+  return rank_goes_wide(Q, m, work) ? launch_rank_wide(F, Q, m, keep, rank, crowd, order, work, s)
+                                    : launch_rank(F, Q, m, keep, rank, crowd, order, s);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // Variation.  Draw layout (include/dkg.h): u[2 w], u[2 w + 1] the tournament of winner w; then per pair k < P / 2
 // its crossover gate; then per (pair, coordinate) three numbers (cross this coordinate, the spread, swap); then per
 // (child, coordinate) two (mutate, the perturbation).
@@ -493,7 +769,7 @@ MeanArgs mean_args(const dkg_output* outs, int m, int d, const double* x, int P,
 
 // dkg_pareto_nsga2's workspace carve
 struct NsgaWs {
-  size_t x2, f2, xn, crowd2, rank2, order, total;
+  size_t x2, f2, xn, crowd2, rank2, order, wide, total;
 };
 NsgaWs nsga_ws(int P, int d, int m) {
   NsgaWs w{};
@@ -510,6 +786,8 @@ NsgaWs nsga_ws(int P, int d, int m) {
   off = up256(off + 2 * (size_t)P * sizeof(int));
   w.order = off;
   off = up256(off + 2 * (size_t)P * sizeof(int));
+  w.wide = off;  // the wide rank's scratch for the 2P points of a generation
+  off = up256(off + wide_ws(2 * P).total);
   w.total = off;
   return w;
 }
@@ -527,15 +805,30 @@ int dkg_posterior_mean(const dkg_output* outs, int m, int d, const double* x, in
   return phip(launch_mean(mean_args(outs, m, d, x, P, mean), (hipStream_t)stream), "posterior_mean_kernel");
 }
 
+size_t dkg_pareto_rank_workspace(int Q, int m) {
+  if (Q < 1 || Q > WR_MAXQ || m < 1 || m > DKG_MAX_OUTPUTS) return 0;
+  return wide_ws(Q).total;
+}
+
 int dkg_pareto_rank(const double* F, int Q, int m, int keep, int* rank, double* crowd, int* order, void* work,
                     size_t work_bytes, void* stream) {
-  (void)work;
-  (void)work_bytes;
   if (Q < 1 || m < 1 || keep < 1 || keep > Q) return pfail(DKG_ERR_ARG, "Q=%d m=%d keep=%d", Q, m, keep);
-  if (Q > PR_MAXQ) return pfail(DKG_ERR_UNSUPPORTED, "Q=%d points (supported <= %d)", Q, PR_MAXQ);
+  if (Q > (work ? WR_MAXQ : PR_MAXQ))
+    return pfail(DKG_ERR_UNSUPPORTED, "Q=%d points (supported <= %d, <= %d with a workspace)", Q, PR_MAXQ, WR_MAXQ);
   if (m > DKG_MAX_OUTPUTS) return pfail(DKG_ERR_UNSUPPORTED, "m=%d objectives (supported <= %d)", m, DKG_MAX_OUTPUTS);
   if (!F || !rank || !crowd || !order) return pfail(DKG_ERR_ARG, "NULL pointer");
-  return phip(launch_rank(F, Q, m, keep, rank, crowd, order, (hipStream_t)stream), "pareto_rank_kernel");
+  if (work && work_bytes < wide_ws(Q).total)
+    return pfail(DKG_ERR_WORKSPACE, "workspace %zu bytes < required %zu", work_bytes, wide_ws(Q).total);
+  return phip(launch_rank_any(F, Q, m, keep, rank, crowd, order, work, (hipStream_t)stream), "dkg_pareto_rank");
+}
+
+int dkg_debug_pareto_wide(int mode) {
+  if (mode < -1 || mode > 1) {
+    pfail(DKG_ERR_ARG, "dkg_debug_pareto_wide: mode=%d (-1 the rule, 0 never below %d points, 1 always)", mode,
+          PR_MAXQ + 1);
+    return -2;
+  }
+  return g_pareto_wide_mode.exchange(mode, std::memory_order_relaxed);
 }
 
 size_t dkg_pareto_draws(int P, int d) {
@@ -581,6 +874,7 @@ int dkg_pareto_nsga2(const dkg_output* outs, int m, int d, const double* lb, con
   double* crowd2 = reinterpret_cast<double*>(ws + w.crowd2);
   int* rank2 = reinterpret_cast<int*>(ws + w.rank2);
   int* order = reinterpret_cast<int*>(ws + w.order);
+  void* wide = ws + w.wide;
   const int Pd = P * d, gb = (Pd + 255) / 256;
   const bool raw = prm->raw_inputs != 0;
   // evaluate `pts` (device [P][d], in the bounds) into `out` [P][m]
@@ -596,7 +890,7 @@ int dkg_pareto_nsga2(const dkg_output* outs, int m, int d, const double* lb, con
   };
   hipLaunchKernelGGL(pareto_init_kernel, dim3(gb), dim3(256), 0, s, uniforms, lb, ub, Pd, d, X);
   if ((st = phip(hipGetLastError(), "pareto_init_kernel")) || (st = evaluate(X, F)) ||
-      (st = phip(launch_rank(F, P, m, P, rank, crowd, order, s), "pareto_rank_kernel")))
+      (st = phip(launch_rank_any(F, P, m, P, rank, crowd, order, wide, s), "pareto_rank_kernel")))
     return st;
   const size_t draws = dkg_pareto_draws(P, d);
   GatherArgs g{order, X2, F2, crowd2, rank2, X, F, crowd, rank, P, d, m};
@@ -610,7 +904,7 @@ int dkg_pareto_nsga2(const dkg_output* outs, int m, int d, const double* lb, con
         (st = phip(hipMemcpyAsync(F2, F, (size_t)P * m * sizeof(double), hipMemcpyDeviceToDevice, s),
                    "hipMemcpyAsync")) ||
         (st = phip(launch_variation(a, s), "pareto_variation_kernel")) || (st = evaluate(Xc, Fc)) ||
-        (st = phip(launch_rank(F2, 2 * P, m, P, rank2, crowd2, order, s), "pareto_rank_kernel")))
+        (st = phip(launch_rank_any(F2, 2 * P, m, P, rank2, crowd2, order, wide, s), "pareto_rank_kernel")))
       return st;
     hipLaunchKernelGGL(pareto_gather_kernel, dim3((gt + 255) / 256), dim3(256), 0, s, g);
     if ((st = phip(hipGetLastError(), "pareto_gather_kernel"))) return st;

@@ -33,7 +33,7 @@ from .metrics import (
     estimate_hypervolume_from_posterior_mean,
 )
 from .model import ModelListGPState, SingleTaskGPState, from_botorch, from_state_dict
-from .pareto import nondominated_rank, posterior_mean, sample_points_on_pareto_front
+from .pareto import nondominated_rank, posterior_front_on_points, posterior_mean, sample_points_on_pareto_front
 from .utils import is_power_of_2, make_torch_std_grid, sample_simplex
 
 __all__ = [
@@ -62,6 +62,7 @@ __all__ = [
     "from_state_dict",
     "posterior_mean",
     "nondominated_rank",
+    "posterior_front_on_points",
     "sample_points_on_pareto_front",
     "calculate_reference_point",
     "estimate_best_possible_expected_performance_after_scalarisation",

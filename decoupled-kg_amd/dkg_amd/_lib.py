@@ -70,6 +70,8 @@ SIGNATURES = {
     "dkg_posterior_mean": (c_int, [POINTER(DkgOutput), c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "dkg_pareto_rank": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                 c_void_p]),
+    "dkg_pareto_rank_workspace": (c_size_t, [c_int, c_int]),
+    "dkg_debug_pareto_wide": (c_int, [c_int]),
     "dkg_pareto_draws": (c_size_t, [c_int, c_int]),
     "dkg_pareto_variation": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                      POINTER(DkgNsga2Params), c_void_p, c_void_p, c_void_p]),

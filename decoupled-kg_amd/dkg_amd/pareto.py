@@ -8,7 +8,8 @@ not available and is not restated: the generations here run the published operat
 listed in DESIGN.md 8c (the tournament draws with replacement, the draw layout is this library's).
 
 * ``posterior_mean``                 ``dkg_posterior_mean``: the mean alone, O(P n) per output
-* ``nondominated_rank``              ``dkg_pareto_rank``
+* ``nondominated_rank``              ``dkg_pareto_rank`` (up to 16384 points)
+* ``posterior_front_on_points``      the non-dominated points of the mean over a candidate set (a grid)
 * ``pareto_variation``               ``dkg_pareto_variation``
 * ``pareto_nsga2``                   ``dkg_pareto_nsga2``: the whole evolution in one call
 * ``sample_points_on_pareto_front``  the reference's entry (numpy in the reference's shapes)
@@ -87,7 +88,9 @@ def nondominated_rank(F, keep: Optional[int] = None, device=None):
     """Non-dominated ranks, crowding distances and survivor order of the points F [Q, m] (all objectives maximised;
     ``dkg_pareto_rank``) -> (rank int32 [Q], crowding float64 [Q], order int32 [Q]) on the device.  Fronts are
     peeled until ``keep`` (default Q) points are ranked; the others get rank -1 and crowding 0, and ``order`` lists
-    the ranked points by (rank, crowding descending, index), then -1."""
+    the ranked points by (rank, crowding descending, index), then -1.  Q <= 16384: the call brings the workspace
+    ``dkg_pareto_rank_workspace`` asks for, so the library ranks Q <= 2048 points with whichever of its two paths
+    its rule names and more points with the wide one; the results do not depend on the path."""
     dev = F.device if isinstance(F, torch.Tensor) and F.is_cuda and device is None else _device(device)
     F = torch.as_tensor(F, dtype=torch.double).detach().to(dev).contiguous()
     if F.dim() != 2:
@@ -97,10 +100,29 @@ def nondominated_rank(F, keep: Optional[int] = None, device=None):
     rank = torch.empty(Q, dtype=torch.int32, device=dev)
     crowd = torch.empty(Q, dtype=torch.double, device=dev)
     order = torch.empty(Q, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    nbytes = int(lib.dkg_pareto_rank_workspace(Q, m))  # 0 outside the limits: the call below reports which
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
     with torch.cuda.device(dev):
-        _lib.check(_lib.load().dkg_pareto_rank(_lib.ptr(F), Q, m, keep, _lib.ptr(rank), _lib.ptr(crowd),
-                                               _lib.ptr(order), None, 0, current_stream_ptr(dev)), "dkg_pareto_rank")
+        _lib.check(lib.dkg_pareto_rank(_lib.ptr(F), Q, m, keep, _lib.ptr(rank), _lib.ptr(crowd), _lib.ptr(order),
+                                       _lib.ptr(work) or None, nbytes, current_stream_ptr(dev)), "dkg_pareto_rank")
     return rank, crowd, order
+
+
+def posterior_front_on_points(model, X, device=None) -> Tuple[np.ndarray, np.ndarray]:
+    """The non-dominated points of the posterior mean over the candidate set X [P, d] (the model's own inputs,
+    P <= 16384) -> (x [k, d], f [k, m]) numpy arrays in index order: ``dkg_posterior_mean`` at X, then
+    ``dkg_pareto_rank`` with ``keep = 1``, and the rows of rank 0.  The deterministic front of a grid or of any
+    candidate set: no random numbers, no generations.  ``model``: a ``ModelListGPState``, a ``SingleTaskGPState``
+    or a ``PreparedModel``."""
+    pm = _prepared(model, device)
+    X = torch.as_tensor(X, dtype=torch.double).detach().to(pm.device).contiguous()
+    f = pm.mean(X)
+    if X.shape[0] == 0:
+        return X.cpu().numpy(), f.cpu().numpy()
+    rank, _, _ = nondominated_rank(f, keep=1)
+    front = rank == 0
+    return X[front].cpu().numpy(), f[front].cpu().numpy()
 
 
 def pareto_draws(P: int, d: int) -> int:

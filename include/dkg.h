@@ -209,7 +209,12 @@ int dkg_mll_value_grad(const dkg_output* outs, int m, int d, const double* const
  * the same bits whatever P is and whichever row holds the point.  P = 0 is a no-op. */
 int dkg_posterior_mean(const dkg_output* outs, int m, int d, const double* x, int P, double* mean, void* stream);
 
-/* Non-dominated ranks, crowding distances and survivor order of Q <= 2048 points F (device [Q][m], m <= 8).
+/* Bytes of device scratch dkg_pareto_rank's wide path needs for Q points of m objectives (dominator counts and
+ * fronts [Q] ints each, a few scalars); 0 outside 1 <= Q <= 16384, 1 <= m <= DKG_MAX_OUTPUTS. */
+size_t dkg_pareto_rank_workspace(int Q, int m);
+
+/* Non-dominated ranks, crowding distances and survivor order of Q points F (device [Q][m], m <= 8): Q <= 2048
+ * without a workspace, Q <= 16384 with one.
  *   dominance: a dominates b iff a >= b in every objective and a > b in at least one (equal points do not
  *              dominate each other)
  *   rank     : fronts are peeled in order (Deb et al. 2002) until at least `keep` points carry a rank
@@ -220,7 +225,17 @@ int dkg_posterior_mean(const dkg_output* outs, int m, int d, const double* x, in
  *              one addition per step, no fused multiply-add
  *   order    : device int [Q]: the ranked points by (rank ascending, crowding descending, index ascending),
  *              then -1; its first `keep` entries are the survivors
- * One workgroup; every loop is bounded by Q.  work / work_bytes: reserved (not read; NULL / 0 are fine). */
+ * The results are integers and one subtraction, division and addition per crowding step, so both paths below
+ * give the same bits.  Every loop of every kernel is bounded by Q; no workgroup waits on another.
+ *   work == NULL: one workgroup (pareto_rank_kernel) ranks the Q <= 2048 points out of its LDS;
+ *                 DKG_ERR_UNSUPPORTED above 2048.  work_bytes is not read.
+ *   work != NULL: device scratch of at least dkg_pareto_rank_workspace(Q, m) bytes (DKG_ERR_WORKSPACE when
+ *                 work_bytes is short; DKG_ERR_UNSUPPORTED for Q > 16384), overwritten by every call and carrying
+ *                 nothing from one call to the next.  2048 < Q <= 16384 runs the wide path: five stream-ordered
+ *                 launches (clear, dominator counts over point tiles x slices of the points, the front peel in one
+ *                 workgroup, crowding and order with one wave per point).  Q <= 2048 runs the path a host rule of
+ *                 (Q, m) names, measured per objective bucket (dkg_debug_pareto_wide overrides it).
+ * Argument checks come before any device work. */
 int dkg_pareto_rank(const double* F, int Q, int m, int keep, int* rank, double* crowd, int* order, void* work,
                     size_t work_bytes, void* stream);
 
@@ -256,7 +271,8 @@ int dkg_pareto_variation(const double* X, const int* rank, const double* crowd, 
                          const double* ub, const dkg_nsga2_params* prm, const double* uniforms, double* children,
                          void* stream);
 
-/* Bytes of device scratch dkg_pareto_nsga2 needs (0 outside the limits above). */
+/* Bytes of device scratch dkg_pareto_nsga2 needs (0 outside the limits above); it includes
+ * dkg_pareto_rank_workspace(2P, m), so its ranks follow dkg_pareto_rank's rule with a workspace. */
 size_t dkg_pareto_workspace(int P, int d, int m);
 
 /* The whole evolution, no host synchronisation inside: what pop = algo.evolve(pop) does at sample.py:40-44.
@@ -523,6 +539,13 @@ long long dkg_debug_cross_tall_launches(void);
  * dimension d and fp32 contractions or not (f32) takes the one-launch cross kernel under the current mode, else 0;
  * -2 on bad arguments.  Host only: no device is touched. */
 int dkg_debug_cross_tall_eligible(int max_n_pad, int d, int B, int f32);
+
+/* Which kernels rank Q <= 2048 points when dkg_pareto_rank has a workspace (and every rank inside
+ * dkg_pareto_nsga2).  mode -1: the measured rule (the default), 0: never the wide path, 1: always the wide path
+ * (tests and A/B measurements).  Same bits either way; Q > 2048 is always the wide path.  Returns the previous
+ * mode; any other value of mode is an error (returns -2, dkg_last_error) and changes nothing.  Read when a call
+ * issues its launches. */
+int dkg_debug_pareto_wide(int mode);
 
 /* Which envelope kernel an initialised plan launches (decided by the LDS arithmetic of dkg_plan_init):
  * out = {register slots per lane of the staged envelope (2, 8, 17 or 33; 0 when the plan streams its lines),
