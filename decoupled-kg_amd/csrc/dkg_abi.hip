@@ -77,9 +77,7 @@ WsLayout layout(const dkg_output* outs, int m, int N, int B, int S, int d = 0, i
   WsLayout L{};
   const size_t Bp = pad16(std::max(B, 1));
   const size_t items = (size_t)(T - 1) * Bp + std::max(B, 1);
-  // fused hand-off counters, one per 128-byte line: cnt1 [m][Bp / 16], cnt2 [ceil(B / 32)], done; then the err word
-  L.sync_bytes = ((((size_t)m * (Bp / 16) + (Bp + 31) / 32 + 1) * HANDOFF_STRIDE * sizeof(unsigned long long) +
-                   sizeof(int)) + 15) & ~(size_t)15;
+  L.sync_bytes = sync_layout(m, std::max(B, 1)).bytes;
   size_t off = align256(L.sync_bytes);
   for (int i = 0; i < m; ++i) {
     if (flags & DKG_PLAN_GRAD) {
@@ -193,10 +191,10 @@ int check_targets(const int* targets, int T, int m) {
 // DKG_PLAN_FORCE_GLOBAL_ROWS this is the staged plan or its refusal; DKG_PLAN_GRAD_GLOBAL_ROWS changes the
 // refusal alone.  Host arithmetic only (dkg_plan_grad_rows).
 int grad_rows_rule(int m, int N, int sw, int S, int d, int max_np, int flags) {
-  const bool fits = envelope_grad_lds_bytes(m, N, sw, S, d, max_np, true) <= 160 * 1024;
+  const bool fits = envelope_lds_bytes(m, N, sw, S, d, max_np, true, true, false) <= 160 * 1024;
   if (fits && !(flags & DKG_PLAN_FORCE_GLOBAL_ROWS)) return 0;
   if ((flags & (DKG_PLAN_GRAD_GLOBAL_ROWS | DKG_PLAN_FORCE_GLOBAL_ROWS)) &&
-      envelope_grad_rows_lds_bytes(m, N, sw, S, max_np) <= 160 * 1024)
+      envelope_lds_bytes(m, N, sw, S, d, max_np, true, true, true) <= 160 * 1024)
     return 1;
   return -fail(DKG_ERR_UNSUPPORTED, "gradient: m=%d outputs, n=%d, d=%d exceed the envelope stage's LDS", m, max_np, d);
 }
@@ -236,10 +234,12 @@ int build_plan(const dkg_output* outs, int m, int d, const double* disc, int N, 
   // the envelope stages the line data in LDS when it fits and the lines fit
   // the register slots; otherwise it streams them from global memory
   const bool want_grad = (flags & DKG_PLAN_GRAD) != 0;
-  bool stream = N + 1 > 64 * 33 || envelope_lds_bytes(m, N, sw, S, false) > 160 * 1024 ||
-                (want_grad && envelope_grad_lds_bytes(m, N, sw, S, d, max_np, false) > 160 * 1024) ||
+  // (envelope_lds_bytes' last three arguments: grad, stream, grows)
+  bool stream = N + 1 > 64 * 33 ||
+                envelope_lds_bytes(m, N, sw, S, d, max_np, false, false, false) > 160 * 1024 ||
+                (want_grad && envelope_lds_bytes(m, N, sw, S, d, max_np, true, false, false) > 160 * 1024) ||
                 (want_grad && (flags & DKG_PLAN_FORCE_GLOBAL_ROWS));
-  if (envelope_lds_bytes(m, N, sw, S, true) > 160 * 1024)
+  if (envelope_lds_bytes(m, N, sw, S, d, max_np, false, true, false) > 160 * 1024)
     return fail(DKG_ERR_UNSUPPORTED, "S=%d x m=%d weights exceed the envelope stage's LDS", S, m);
   if (!weights || !workspace || (N > 0 && !disc)) return fail(DKG_ERR_ARG, "NULL data pointer");
   for (int i = 0; i < m; ++i)
@@ -323,11 +323,7 @@ int build_plan(const dkg_output* outs, int m, int d, const double* disc, int N, 
   const bool split_stages = !(flags & DKG_PLAN_FUSED) || (flags & DKG_PLAN_FORCE_WALK);
   P->sync = reinterpret_cast<unsigned long long*>(ws);
   P->sync_bytes = L.sync_bytes;
-  {
-    const size_t words = ((size_t)m * (pad16(std::max(max_B, 1)) / 16) + (pad16(std::max(max_B, 1)) + 31) / 32 + 1) *
-                         HANDOFF_STRIDE;
-    P->sync_err = reinterpret_cast<int*>(ws + words * sizeof(unsigned long long));
-  }
+  P->sync_err = reinterpret_cast<int*>(P->sync + sync_layout(m, std::max(max_B, 1)).err);
   P->fused = (!split_stages && !P->f32 && !P->stream && N >= 1 && N + 1 <= 64 * 17 && !P->debug_env && !P->debug_cov &&
               !DKG_ABLATIONS && fused_lds_bytes_host(*P) <= 160 * 1024)
                  ? 1
@@ -816,7 +812,7 @@ int dkg_plan_grad_rows(const dkg_output* outs, int m, int d, int N, int S, int f
   if (N > (1 << 22)) return -fail(DKG_ERR_UNSUPPORTED, "N=%d discretisation points (supported <= %d)", N, 1 << 22);
   int sw, split;
   envelope_geometry(S, &sw, &split);
-  if (envelope_lds_bytes(m, N, sw, S, true) > 160 * 1024)
+  if (envelope_lds_bytes(m, N, sw, S, d, max_np_of(outs, m), false, true, false) > 160 * 1024)
     return -fail(DKG_ERR_UNSUPPORTED, "S=%d x m=%d weights exceed the envelope stage's LDS", S, m);
   if ((st = check_plan_flags(flags))) return -st;
   if (!(flags & DKG_PLAN_GRAD)) return -fail(DKG_ERR_ARG, "dkg_plan_grad_rows: flags 0x%x lack DKG_PLAN_GRAD", flags);
@@ -1050,6 +1046,18 @@ int dkg_debug_plan_envelope(const void* host_plan, int out[4]) {
   out[2] = h.sw;
   out[3] = h.split;
   return 0;
+}
+
+int dkg_debug_envelope_lds(int m, int N, int waves, int S, int d, int max_np, int grad, int stream, int grows,
+                           int out[DKG_ENV_LDS_REGIONS + 1]) {
+  if (!out) return fail(DKG_ERR_ARG, "dkg_debug_envelope_lds: out is NULL");
+  if (m < 1 || m > DKG_MAX_OUTPUTS || N < 0 || N > (1 << 22) || waves < 1 || waves > 8 || S < 1 ||
+      (long long)S * m > (1 << 24) || d < 1 || d > DKG_MAX_DIM || max_np < 16 || max_np > 1024 || max_np % 16 != 0)
+    return fail(DKG_ERR_ARG, "dkg_debug_envelope_lds: m=%d N=%d waves=%d S=%d d=%d max_np=%d", m, N, waves, S, d, max_np);
+  if (grows && !(grad && stream))
+    return fail(DKG_ERR_ARG, "dkg_debug_envelope_lds: global rows are the streaming gradient envelope's alone");
+  envelope_lds_regions(m, N, waves, S, d, max_np, grad != 0, stream != 0, grows != 0, out);
+  return DKG_OK;
 }
 
 int dkg_debug_wave_ops(const double* in, double* out, void* stream) {

@@ -574,6 +574,25 @@ constexpr unsigned HANDOFF_SPIN_LIMIT = 1u << 18;
 // Counters sit one per 128-byte line (16 words apart): hundreds of workgroups poll them at once, and
 // pollers of different counters must not queue on one line (MI355X_MICROARCH.md row "polling-cost").
 constexpr int HANDOFF_STRIDE = 16;
+// Candidates per row block of cnt2 (the covariance stage's 16 * PC_RB).
+constexpr int HANDOFF_RB_ROWS = 32;
+
+// The counter block at Plan::sync for m outputs and B >= 1 candidates, in words: cnt1 [m][rt], cnt2 [nrb], done,
+// then the err word (an int); `bytes` covers all of it, rounded up to 16.  A plan sizes the block for max_B and
+// keeps err there; a launch lays the counters out for its own B (it re-zeroes the range it used).
+struct SyncLayout {
+  size_t cnt1, cnt2, done, err, bytes;
+};
+inline SyncLayout sync_layout(int m, int B) {
+  const size_t rt = pad16(B) / 16, nrb = (pad16(B) + HANDOFF_RB_ROWS - 1) / HANDOFF_RB_ROWS;
+  SyncLayout L;
+  L.cnt1 = 0;
+  L.cnt2 = L.cnt1 + (size_t)m * rt * HANDOFF_STRIDE;
+  L.done = L.cnt2 + nrb * HANDOFF_STRIDE;
+  L.err = L.done + HANDOFF_STRIDE;
+  L.bytes = (L.err * sizeof(unsigned long long) + sizeof(int) + 15) & ~(size_t)15;
+  return L;
+}
 
 template <bool WT, class T>
 __device__ __forceinline__ void st_out(T* p, T v) {

@@ -1430,6 +1430,83 @@ __host__ __device__ inline int stage_stride(int N, int rec) {
   return (stage_len(N * rec) > slots ? stage_len(N * rec) : slots) + STAGE_FRONT;
 }
 
+// The dynamic LDS of the envelope kernels (envelope_body): where every region starts, in doubles from the
+// base, in layout order.  The one statement of the layout: the kernel takes its pointers from it and the host
+// its byte counts (envelope_lds_bytes).  A region the mode does not have is -1.
+struct EnvLds {
+  int SLp;   // stride of one staged record array (stage_stride); 0 when the lines stream
+  int LC;    // survivor-list capacity per wave (list_cap)
+  int NPS;   // GRAD: row stride of qrow / jrow, whole DMA pieces
+  // [0, lmu): STAGE_FRONT doubles of front pad (line k >= 1 reads record k - 1: the lane-0 / slot-0 read of
+  // record -1 lands here)
+  int lmu;   // [SLp]       mu_D records [N][rec]
+  int lcv;   // [SLp]       the candidate's covariance records [N][rec]
+  int lw;    // [S m]       the weights (rounded up to a 16-byte piece)
+  int skg;   // [S]         KG_j of the group's pairs, summed in j order (rounded up likewise)
+  int sbuf;  // [SW][2][LC] per wave: the survivor list's slopes and intercepts
+  // forward
+  int cbuf;  // streaming: the quickhull refinement's vertex arrays [SW][VREG], or (stream_staged) the four
+             // staged chunk buffers [4][staged_chunk_len], whose room the refinement reuses after the passes
+  int sif;   // [SW][LC] ints: the list's line indices
+  // gradient
+  int sidx;  // [SW][ENV_CAP] ints: the list's line indices
+  int qrow;  // [M][NPS]    the candidate's q_i rows      } not with GROWS: the rows stay in global memory
+  int jrow;  // [M][d][NPS] the candidate's J_i rows      }
+  int sgv;   // [M][16]     d v_i / dx
+  int sgm;   // [M][16]     d mu_i / dx
+  int sgw;   // [SW][64]    per wave: gacc | ga0 | gvv | gtot
+  int sx;    // [16]        x_b
+  int sil;   // [M][16]     1 / lengthscale per output
+  int shD;   // [SW][HCAP]  per wave: pending hull lines' dE/db
+  int suw;   // [SW][NP]    per wave: u_i = sum_h coef_h Q_D,i[k_h]
+  int sscl;  // [SW][ENV_CAP] per wave: left breakpoints of hull vertices
+  int shk;   // [SW][HCAP] ints: pending hull lines' indices
+  int total;
+};
+
+// M: the output bucket (the kernel's template parameter), m <= M the plan's outputs, SW waves per workgroup,
+// NP the widest padded training size (Plan::max_np).  grad / stream / grows: envelope_body's GRAD / STREAM / GROWS.
+__host__ __device__ __forceinline__ EnvLds env_lds(int M, int m, int N, int SW, int S, int d, int NP, bool grad,
+                                                   bool stream, bool grows) {
+  EnvLds L;
+  const int rec = cov_rec(M);  // doubles per line record
+  L.SLp = stream ? 0 : stage_stride(N, rec);
+  L.LC = list_cap(stream && !grad);
+  L.NPS = stage_len(NP);
+  L.lmu = STAGE_FRONT;
+  L.lcv = L.lmu + L.SLp;
+  L.lw = L.lcv + L.SLp;
+  L.skg = L.lw + ((S * m + 1) & ~1);
+  L.sbuf = L.skg + ((S + 1) & ~1);
+  const int lists_end = L.sbuf + SW * 2 * L.LC;
+  L.cbuf = L.sif = -1;
+  L.sidx = L.qrow = L.jrow = L.sgv = L.sgm = L.sgw = L.sx = L.sil = L.shD = L.suw = L.sscl = L.shk = -1;
+  if (!grad) {  // (cbuf is empty when the lines are staged)
+    const int verts = SW * VREG, chunks = stream_staged(M) ? 4 * staged_chunk_len(rec) : 0;
+    L.cbuf = lists_end;
+    L.sif = L.cbuf + (!stream ? 0 : chunks > verts ? chunks : verts);
+    L.total = L.sif + (SW * L.LC + 1) / 2;
+    return L;
+  }
+  L.sidx = lists_end;
+  L.sgv = L.sidx + (SW * ENV_CAP + 1) / 2;
+  if (!grows) {
+    L.qrow = L.sgv;
+    L.jrow = L.qrow + M * L.NPS;
+    L.sgv = L.jrow + M * d * L.NPS;
+  }
+  L.sgm = L.sgv + M * DKG_MAX_DIM;
+  L.sgw = L.sgm + M * DKG_MAX_DIM;
+  L.sx = L.sgw + SW * 64;
+  L.sil = L.sx + DKG_MAX_DIM;
+  L.shD = L.sil + M * DKG_MAX_DIM;
+  L.suw = L.shD + SW * HCAP;
+  L.sscl = L.suw + SW * NP;
+  L.shk = L.sscl + SW * ENV_CAP;
+  L.total = L.shk + (SW * HCAP + 1) / 2;
+  return L;
+}
+
 // Async global -> LDS copy of n doubles (16 B per lane per wave instruction,
 // global_load_lds_dwordx4): the data never touches VGPRs and every piece of
 // every wave is in flight at once.  `dst` has stage_len(n) doubles of room.
@@ -1524,22 +1601,17 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
     cv_src[i] = cov_all + (size_t)b * cov_stride;  // records of candidate b
   }
 
-  // LDS: [pad][mu_i over D] per output, [pad][cov_i over D] per output (line
-  // k >= 1 reads index k - 1; the pad makes the lane-0 / slot-0 read legal),
-  // the weights, then the per-wave survivor lists.
+  // the dynamic LDS regions (EnvLds)
   constexpr int MP = cov_rec(M);  // doubles per line record
-  const int SLp = STREAM ? 0 : stage_stride(N, MP);
-  constexpr int LC = list_cap(STREAM && !GRAD);  // survivor-list capacity per wave
-  double* lmu = smem + STAGE_FRONT;
-  double* lcv = lmu + SLp;
-  double* lw = lcv + SLp;
-  double* skg = lw + ((S * m + 1) & ~1);  // KG_j of the group's pairs (summed in j order)
-  double* sbuf = skg + ((S + 1) & ~1);
-  // GRAD regions: per-wave index lists, per-wave Q_D accumulators u_i[c], the
-  // candidate's q_i and J_i rows, gv / gm / per-wave gradient scratch, x_b.
   const int d = P->d;
   const int NP = P->max_np;
-  const int NPS = stage_len(NP);  // GRAD: LDS row stride of the candidate's q_i / J_i rows
+  const EnvLds L = env_lds(M, m, N, SW, S, d, NP, GRAD, STREAM, GROWS);
+  const int LC = L.LC, NPS = L.NPS;
+  double* lmu = smem + L.lmu;
+  double* lcv = smem + L.lcv;
+  double* lw = smem + L.lw;
+  double* skg = smem + L.skg;
+  double* sbuf = smem + L.sbuf;
   const double* disc = GRAD ? P->disc : nullptr;
   // test hook (DKG_PLAN_FORCE_WALK): every pair takes the list-overflow path
   const bool force_walk = __builtin_amdgcn_readfirstlane(P->debug_env) & 1;
@@ -1548,23 +1620,25 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
   double *sil = nullptr, *shD = nullptr, *suw = nullptr, *sscl = nullptr;
   int* shk = nullptr;
   if constexpr (GRAD) {
-    double* gb = sbuf + (size_t)SW * 2 * LC;
-    sidx = reinterpret_cast<int*>(gb);
-    if constexpr (GROWS) {
-      sgv = gb + (SW * ENV_CAP + 1) / 2;             // no qrow / jrow: the rows stay in global memory
-    } else {
-      qrow = gb + (SW * ENV_CAP + 1) / 2;
-      jrow = qrow + (size_t)M * NPS;                 // rows of stride NPS: whole DMA pieces
-      sgv = jrow + (size_t)M * d * NPS;              // [M][16]  d v_i / dx
+    // each pointer from the one before it, by the difference of their offsets: the pointer chain these regions
+    // were first carved by, which the gradient kernels' code stays closest to
+    double* at = sbuf;
+    int at_off = L.sbuf;
+    auto region = [&](int off) { at += off - at_off; at_off = off; return at; };
+    sidx = reinterpret_cast<int*>(region(L.sidx));
+    if constexpr (!GROWS) {
+      qrow = region(L.qrow);
+      jrow = region(L.jrow);
     }
-    sgm = sgv + M * DKG_MAX_DIM;                     // [M][16]  d mu_i / dx
-    sgw = sgm + M * DKG_MAX_DIM;                     // [SW][64] per wave: gacc | ga0 | gvv | gtot
-    sx = sgw + SW * 64;                              // [16]     x_b
-    sil = sx + DKG_MAX_DIM;                          // [M][16]  1 / lengthscale per output
-    shD = sil + M * DKG_MAX_DIM;                     // [SW][HCAP] per wave: pending hull lines' dE/db
-    suw = shD + SW * HCAP;                           // [SW][NP]   per wave: u_i = sum_h coef_h Q_D,i[k_h]
-    sscl = suw + (size_t)SW * NP;                    // [SW][ENV_CAP] per wave: left breakpoints of hull vertices
-    shk = reinterpret_cast<int*>(sscl + SW * ENV_CAP);  // [SW][HCAP] pending hull lines' indices
+    sgv = region(L.sgv);
+    sgm = region(L.sgm);
+    sgw = region(L.sgw);
+    sx = region(L.sx);
+    sil = region(L.sil);
+    shD = region(L.shD);
+    suw = region(L.suw);
+    sscl = region(L.sscl);
+    shk = reinterpret_cast<int*>(region(L.shk));
   }
 
   // ---- one round of memory traffic: DMA the line data, plain loads for the rest
@@ -1719,17 +1793,13 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
 
   double* sb = sbuf + (size_t)wave * 2 * LC;
   double* sa = sb + LC;
-  // streaming forward: the quickhull refinement's vertex arrays after the lists
-  // staged streaming forward: the chunk buffers take the vertex arrays' place (the refinement runs
-  // after the staged passes, so it reuses their room)
+  // staged streaming forward: the chunk buffers and the refinement's vertex arrays share cbuf (the refinement
+  // runs after the staged passes)
   constexpr bool STG = STREAM && !GRAD && stream_staged(M);
   constexpr int CBL = STG ? staged_chunk_len(cov_rec(M)) : 0;
-  const int vreg_room = STG ? max(SW * VREG, 4 * CBL) : ((STREAM && !GRAD) ? SW * VREG : 0);
-  double* cbuf = sbuf + (size_t)SW * 2 * LC;
+  double* cbuf = smem + L.cbuf;
   double* vreg = cbuf + (size_t)wave * VREG;
-  // forward: the list's line indices after the vertex arrays (GRAD: sidx)
-  int* sif = reinterpret_cast<int*>(sbuf + (size_t)SW * 2 * LC + vreg_room) +
-             (size_t)wave * LC;
+  int* sif = reinterpret_cast<int*>(smem + L.sif) + (size_t)wave * LC;  // forward (GRAD: sidx)
   int* si = nullptr;
   double* gw = nullptr;
   if constexpr (GRAD) {

@@ -28,6 +28,8 @@
 
 namespace dkg {
 
+static_assert(16 * PC_RB == HANDOFF_RB_ROWS, "cnt2 counts the covariance stage's row blocks");
+
 struct FusedArgs {
   const Plan* P;
   const double* xnew;
@@ -88,8 +90,8 @@ forward_fused_kernel(FusedArgs a) {
     const int v = id - a.nC;
     const int m = P->m;
     const int bx = v % a.vcols, oi = (v / a.vcols) % m, by = v / (a.vcols * m);
-    double* part = smem;                                  // [(PC_KS - 1) * 2 PC_RB * 4 * 64]
-    double* qpart = smem + (PC_KS - 1) * 2 * PC_RB * 4 * 64;
+    double* part = smem;
+    double* qpart = smem + PC_PART;
     posterior_cov_body<DM, double, true>(P, a.xnew, a.B, bx, by, oi, part, qpart, kst_slot_wg(a.dst, P, 1, v), &a.ho);
     return;
   }
@@ -101,8 +103,10 @@ forward_fused_kernel(FusedArgs a) {
 
 // Dynamic LDS of the fused launch: the largest of its roles'.
 inline size_t fused_lds_bytes(const Plan& h) {
-  const size_t cov = ((size_t)(PC_KS - 1) * 2 * PC_RB * 4 * 64 + (size_t)(PC_KS - 1) * 2 * PC_RB * 16) * sizeof(double);
-  return std::max({cross_root_lds_bytes(h.max_np, h.d), envelope_lds_bytes(h.m, h.N, 8, h.S, false), cov});
+  const size_t cov = (size_t)(PC_PART + PC_QPART) * sizeof(double);
+  // (the envelope role: 8 waves, staged forward)
+  const size_t env = envelope_lds_bytes(h.m, h.N, 8, h.S, h.d, h.max_np, false, false, false);
+  return std::max({cross_root_lds_bytes(h.max_np, h.d), env, cov});
 }
 
 template <int DM, int MAXL, int M>

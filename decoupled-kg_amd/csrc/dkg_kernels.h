@@ -220,9 +220,6 @@ struct XArg {
 // hout (nullable): pinned host [kg (B) | dkg (B x d)] written by the envelope stage itself (split <= 2).
 hipError_t launch_forward_grad(const Plan& h, const Plan* dev, const double* xnew, int B, double* kg, double* dkg,
                                hipStream_t s, const XArg* xa = nullptr, double* hout = nullptr);
-size_t envelope_grad_lds_bytes(int m, int N, int waves, int S, int d, int max_np, bool stream);
-// The same for the global-rows variant (streaming only): no q_i / J_i rows.
-size_t envelope_grad_rows_lds_bytes(int m, int N, int waves, int S, int max_np);
 // One stage of the forward (0 cross_root, 1 posterior_cov, 2 envelope) on stream s.  geom_B (0: B) is the
 // batch size the covariance block shape is chosen for: a launch over K batches of geom_B candidates
 // (dkg_plan_forward_batches) takes the blocks of one geom_B forward, so its results are those of K forwards.
@@ -263,9 +260,14 @@ hipError_t launch_debug_mfma(const double* a, const double* b, double* c, hipStr
 // Launch geometry of the envelope stage for S scalarisation pairs: waves per workgroup and
 // workgroups per candidate.
 void envelope_geometry(int S, int* waves_per_wg, int* split);
-// Dynamic LDS bytes of the envelope kernels.  Not streaming: the covariance records and the mu_D records are
-// both staged (forward, gradient and fused envelopes alike).
-size_t envelope_lds_bytes(int m, int N, int waves, int S, bool stream, bool grad = false);
+// Dynamic LDS bytes of an envelope launch: the total of the kernels' own layout (dkg_device.h env_lds) for the
+// plan's shape and the kernel's mode (envelope_body's GRAD / STREAM / GROWS; grows: global rows, with grad and
+// stream only).  d and max_np count in the gradient's regions alone.
+size_t envelope_lds_bytes(int m, int N, int waves, int S, int d, int max_np, bool grad, bool stream, bool grows);
+// That layout's region offsets (doubles; -1: not in this mode) in layout order, then the total
+// (dkg_debug_envelope_lds).
+void envelope_lds_regions(int m, int N, int waves, int S, int d, int max_np, bool grad, bool stream, bool grows,
+                          int out[DKG_ENV_LDS_REGIONS + 1]);
 size_t cross_root_lds_bytes(int np, int d);
 
 }  // namespace dkg

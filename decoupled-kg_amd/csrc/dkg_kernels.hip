@@ -383,39 +383,19 @@ size_t cross_root_lds_bytes(int np, int d) { return cross_lds_doubles(np, d, cro
 
 static int outputs_bucket(int m) { return m <= 1 ? 1 : m <= 2 ? 2 : m <= 3 ? 3 : m <= 4 ? 4 : 8; }
 
-size_t envelope_lds_bytes(int m, int N, int waves, int S, bool stream, bool grad) {
-  const int M = outputs_bucket(m);
-  const size_t staged = stream ? 0 : 2 * (size_t)stage_stride(N, cov_rec(M));  // the covariance and mu_D records
-  const bool refine = stream && !grad;  // streaming forward: long lists + quickhull vertex arrays
-  const size_t lc = list_cap(refine);
-  // per wave: the list (slopes, intercepts; forward: line indices) and the streaming vertex arrays
-  // streaming forward: the quickhull vertex arrays, or (M = 2..4) the staged chunk buffers in their place
-  const size_t vroom = !refine ? 0
-                       : stream_staged(M) ? std::max((size_t)waves * VREG, (size_t)4 * staged_chunk_len(cov_rec(M)))
-                                          : (size_t)waves * VREG;
-  // the kernel's layout (envelope_body): STAGE_FRONT doubles, the staged arrays, weights, pair sums, lists
-  return ((size_t)STAGE_FRONT + staged + ((S * m + 1) & ~1) + ((S + 1) & ~1) + (size_t)waves * 2 * lc + vroom +
-          (grad ? 0 : ((size_t)waves * lc + 1) / 2)) * sizeof(double);
+// The envelope kernels' own layout (env_lds) for a plan's shape: its region offsets and total, and the bytes.
+void envelope_lds_regions(int m, int N, int waves, int S, int d, int max_np, bool grad, bool stream, bool grows,
+                          int out[DKG_ENV_LDS_REGIONS + 1]) {
+  const EnvLds L = env_lds(outputs_bucket(m), m, N, waves, S, d, max_np, grad, stream, grows);
+  const int r[DKG_ENV_LDS_REGIONS + 1] = {0,      L.lmu, L.lcv, L.lw,  L.skg, L.sbuf, L.cbuf,
+                                          L.sif,  L.sidx, L.qrow, L.jrow, L.sgv, L.sgm, L.sgw,
+                                          L.sx,   L.sil, L.shD, L.suw, L.sscl, L.shk, L.total};
+  std::copy(r, r + DKG_ENV_LDS_REGIONS + 1, out);
 }
 
-size_t envelope_grad_lds_bytes(int m, int N, int waves, int S, int d, int max_np, bool stream) {
-  const int M = outputs_bucket(m);
-  const size_t extra = (size_t)(waves * ENV_CAP + 1) / 2 + (size_t)M * stage_len(max_np) +
-                       (size_t)M * d * stage_len(max_np) +
-                       2 * (size_t)M * DKG_MAX_DIM + (size_t)waves * 64 + DKG_MAX_DIM +
-                       (size_t)M * DKG_MAX_DIM + (size_t)waves * (HCAP + max_np + ENV_CAP) +
-                       (size_t)(waves * HCAP + 1) / 2;
-  return envelope_lds_bytes(m, N, waves, S, stream, true) + extra * sizeof(double);
-}
-
-// Global rows (envelope_body GROWS): the streaming gradient envelope's layout without the M (d + 1) rows of
-// stage_len(max_np) doubles; what grows with n is the per-wave u_i vector alone.
-size_t envelope_grad_rows_lds_bytes(int m, int N, int waves, int S, int max_np) {
-  const int M = outputs_bucket(m);
-  const size_t extra = (size_t)(waves * ENV_CAP + 1) / 2 + 2 * (size_t)M * DKG_MAX_DIM + (size_t)waves * 64 +
-                       DKG_MAX_DIM + (size_t)M * DKG_MAX_DIM + (size_t)waves * (HCAP + max_np + ENV_CAP) +
-                       (size_t)(waves * HCAP + 1) / 2;
-  return envelope_lds_bytes(m, N, waves, S, true, true) + extra * sizeof(double);
+size_t envelope_lds_bytes(int m, int N, int waves, int S, int d, int max_np, bool grad, bool stream, bool grows) {
+  if ((long long)S * m > (1 << 24)) return SIZE_MAX;  // weights far past any LDS, and past what the offsets count
+  return (size_t)env_lds(outputs_bucket(m), m, N, waves, S, d, max_np, grad, stream, grows).total * sizeof(double);
 }
 
 // ---------------------------------------------------------------------------
@@ -877,7 +857,8 @@ hipError_t launch_stage(const Plan& h, const Plan* dev, const double* xnew, int 
   }
   // (several targets: ntgt items per candidate, the workgroups of a candidate's items side by side)
   EnvLaunch a{&h, dev, B, kg, pairs, dim3(xcd_group_size(B, h.split * h.ntgt)), dim3(h.sw * WAVE),
-              envelope_lds_bytes(h.m, h.N, h.sw, h.S, h.stream != 0), s, h.debug_stamp, nullptr, nullptr};
+              envelope_lds_bytes(h.m, h.N, h.sw, h.S, h.d, h.max_np, false, h.stream != 0, false), s, h.debug_stamp,
+              nullptr, nullptr};
   return launch_env<false>(h, a);
 }
 
@@ -907,8 +888,7 @@ hipError_t launch_forward_grad(const Plan& h, const Plan* dev, const double* xne
   if (e != hipSuccess) return e;
   if ((e = launch_stage(h, dev, xnew, B, kg, nullptr, s, 1)) != hipSuccess) return e;  // cov rows, variances
   EnvLaunch a{&h, dev, B, kg, nullptr, dim3(xcd_group_size(B, h.split * h.ntgt)), dim3(h.sw * WAVE),
-              h.grad_rows ? envelope_grad_rows_lds_bytes(h.m, h.N, h.sw, h.S, h.max_np)
-                          : envelope_grad_lds_bytes(h.m, h.N, h.sw, h.S, h.d, h.max_np, h.stream != 0),
+              envelope_lds_bytes(h.m, h.N, h.sw, h.S, h.d, h.max_np, true, h.stream != 0, h.grad_rows != 0),
               s, h.debug_stamp, xnew, dkg, hout};
   return launch_env<true>(h, a);
 }
@@ -951,9 +931,10 @@ hipError_t launch_forward_auto(const Plan& h, const Plan* dev, const double* xne
   a.cov_stride = (long long)h.cov_stride;
   a.bpad = h.bpad;
   // counters laid out for this B (every launch re-zeroes the range it used)
-  a.ho.cnt1 = h.sync;
-  a.ho.cnt2 = h.sync + (size_t)h.m * rt * HANDOFF_STRIDE;
-  a.ho.done = a.ho.cnt2 + (size_t)a.vrows * HANDOFF_STRIDE;
+  const SyncLayout sl = sync_layout(h.m, B);
+  a.ho.cnt1 = h.sync + sl.cnt1;
+  a.ho.cnt2 = h.sync + sl.cnt2;
+  a.ho.done = h.sync + sl.done;
   a.ho.err = h.sync_err;
   a.ho.rt = rt;
   a.ho.nrb = a.vrows;

@@ -398,6 +398,9 @@ __device__ __forceinline__ void cross_root_impl(const dkg_output& o, int d, cons
 constexpr int PC_WAVES = 8;
 constexpr int PC_RB = 2;  // 16-row tiles per workgroup (32 candidates); 2 column tiles (32 lines)
 constexpr int PC_KS = PC_WAVES / (2 * PC_RB);  // K splits: the waves of one tile
+// posterior_cov_body's LDS (doubles): the partial tiles of K splits 1.. (`part`), then their q sums (`qpart`)
+constexpr int PC_PART = (PC_KS - 1) * 2 * PC_RB * 4 * 64;
+constexpr int PC_QPART = (PC_KS - 1) * 2 * PC_RB * 16;
 constexpr int PC_P = 8;  // 16-byte words per operand per load batch (16 k-blocks)
 
 // T = float (DKG_PLAN_F32): the contraction Q_X . Q_D in fp32 (quad-packed
@@ -2333,8 +2336,8 @@ template <int DM, class T = double>
 __global__ __launch_bounds__(PC_WAVES * WAVE) __attribute__((amdgpu_waves_per_eu(DKG_PC_WPE))) void posterior_cov_kernel(const Plan* __restrict__ P,
                                                                          const double* __restrict__ xnew, int B,
                                                                          int dst) {
-  __shared__ __attribute__((aligned(16))) double part[(PC_KS - 1) * 2 * PC_RB * 4 * 64];  // K-split 1.. partial tiles
-  __shared__ double qpart[(PC_KS - 1) * 2 * PC_RB * 16];
+  __shared__ __attribute__((aligned(16))) double part[PC_PART];
+  __shared__ double qpart[PC_QPART];
   unsigned long long* st = kst_slot(dst, P, 1);
   if (DKG_ABLATIONS && (__builtin_amdgcn_readfirstlane(P->debug_cov) & 1)) return;  // ablation: empty covariance stage
   // 1-D grid, the outputs of one 32 x 32 block side by side on one XCD (xcd_group)

@@ -145,6 +145,7 @@ SIGNATURES = {
     "dkg_debug_cross_tall_eligible": (c_int, [c_int, c_int, c_int, c_int]),
     "dkg_debug_plan_envelope": (c_int, [c_void_p, POINTER(c_int)]),
     "dkg_debug_mfma_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dkg_debug_envelope_lds": (c_int, [c_int] * 9 + [POINTER(c_int)]),
 }
 
 _lib = None

@@ -553,6 +553,17 @@ int dkg_debug_pareto_wide(int mode);
  * -2 when host_plan or out is NULL (dkg_last_error).  Host only: no device is touched. */
 int dkg_debug_plan_envelope(const void* host_plan, int out[4]);
 
+/* The dynamic LDS of the envelope kernels for a shape (m outputs, N discretisation points, `waves` waves per
+ * workgroup, S scalarisations, input dimension d, widest padded training size max_np) and a kernel mode (grad,
+ * stream; grows: global rows, with grad and stream only): the offset in doubles of every region in layout order
+ * (DESIGN.md 4.13 names them; -1: the mode has no such region), then the total in doubles.  The same arithmetic
+ * the kernels carve their LDS by and dkg_plan_init sizes and refuses by.  Returns DKG_OK, or DKG_ERR_ARG for a
+ * NULL pointer or a shape outside 1 <= m <= 8, 0 <= N <= 2^22, 1 <= waves <= 8, S >= 1 (S m <= 2^24),
+ * 1 <= d <= 16, max_np a multiple of 16 in [16, 1024], or grows without grad and stream.  Host only. */
+#define DKG_ENV_LDS_REGIONS 20
+int dkg_debug_envelope_lds(int m, int N, int waves, int S, int d, int max_np, int grad, int stream, int grows,
+                           int out[DKG_ENV_LDS_REGIONS + 1]);
+
 /* ---- Launcher: captured forward graphs of several streams enqueued side by side from host threads.
  * A hipGraphLaunch costs ~1 us of host time per kernel node plus ~9 us; one thread launching every
  * stream's graphs in turn leaves the last stream idle for the others' launches.  The
