@@ -25,6 +25,7 @@ from .gp_state import (
     set_incremental_state,
     state_stats,
 )
+from .jes import compute_sample_box_decomposition, qLowerBoundMultiObjectiveJointEntropySearch
 from .metrics import (
     calculate_reference_point,
     estimate_best_possible_expected_performance_after_scalarisation,
@@ -45,6 +46,8 @@ __all__ = [
     "calculate_discrete_kg_conditioning_on_single_output",
     "clear_state_cache",
     "kg_from_lines",
+    "qLowerBoundMultiObjectiveJointEntropySearch",
+    "compute_sample_box_decomposition",
     "normalise_targets",
     "t_batch_mode_transform",
     "BotorchTensorDimensionError",

@@ -30,6 +30,8 @@ DKG_PLAN_FORCE_GLOBAL_ROWS = 128  # test hook, with GRAD: the streaming global-r
 DKG_COV_ENABLE_BLK, DKG_COV_ENABLE_REC2, DKG_COV_ENABLE_REG = 1, 2, 4
 MAX_OUTPUTS = 8
 MAX_DIM = 16
+# include/dkg.h: the limits of the joint entropy search plan (dkg_jes_init)
+DKG_JES_MAX_SAMPLES, DKG_JES_MAX_BOXES, DKG_JES_MAX_CANDIDATES = 64, 4096, 65536
 
 (DKG_OK, DKG_ERR_ARG, DKG_ERR_UNSUPPORTED, DKG_ERR_WORKSPACE, DKG_ERR_HIP, DKG_ERR_NO_LINES,
  DKG_ERR_NOT_PD) = range(7)
@@ -79,6 +81,11 @@ SIGNATURES = {
     "dkg_pareto_nsga2": (c_int, [POINTER(DkgOutput), c_int, c_int, c_void_p, c_void_p, c_int, c_int,
                                  POINTER(DkgNsga2Params), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_size_t, c_void_p]),
+    "dkg_jes_plan_bytes": (c_size_t, []),
+    "dkg_jes_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "dkg_jes_init": (c_int, [POINTER(DkgOutput), c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                             c_size_t, c_void_p, c_void_p]),
+    "dkg_jes_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dkg_abi_version": (c_int, []),
     "dkg_last_error": (c_char_p, []),
     "dkg_frag_elems": (c_size_t, [c_int, c_int]),

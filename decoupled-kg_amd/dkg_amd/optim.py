@@ -19,6 +19,9 @@ On the device a chunk's value + gradient is one C call for all of its restarts
 same launch; the reference uses ``batch_limit = 1`` because its forward is a Python loop over
 candidates (``pipeline/nodes/bo_loop.py:127-129``).  ``batch_limit`` keeps BoTorch's meaning:
 restarts in one chunk share one L-BFGS-B problem (the sum of their values).
+
+``JesOptimisationSpec`` (``acquisition_optimisation_strategy.py:447-552``) runs the same ``optimize_acqf`` on
+the device joint entropy search (``dkg_amd.jes``).
 """
 
 from __future__ import annotations
@@ -337,3 +340,90 @@ class DiscreteKgOptimisationSpec:
         """:143-163 — clip negative values to 0, maximise value / cost, ties to the cheaper objective."""
         best_i, best_x, best_acq_value = max(candidates, key=lambda x: (max(x[-1], 0) / costs[x[0]], -costs[x[0]]))
         return best_i, best_x, best_acq_value / costs[best_i]
+
+
+class JesOptimisationSpec:
+    """``JesOptimisationSpec`` (``acquisition_optimisation_strategy.py:447-552``) on the device joint entropy
+    search: the reference's constructor arguments, its two entry points and its ``_choose_best_objective`` rule
+    (JES carries no cost-aware utility, so the decoupled decision is value per cost, :511-513).
+
+    ``pareto_sampler(model, bounds, num_samples, target_num_points) -> (pareto_sets, pareto_fronts)`` is required:
+    the reference samples GP paths by random Fourier features, runs NSGA-II on each and prunes the fronts
+    (``sample_discrete_pareto_optimal_points``, ``jes_sample_pareto.py``), which is not built here.  The sets are
+    in the model's input space (the unit cube), the fronts in the untransformed output space; samples may hold
+    different numbers of points.  The boxes come from ``compute_sample_box_decomposition`` (one or two
+    objectives; ``hypercell_bounds_fn(pareto_fronts)`` replaces it for more).
+    """
+
+    def __init__(self, estimation_type: str, num_pareto_samples: int, num_pareto_points: int, num_restarts: int,
+                 raw_samples: int, batch_limit: int, max_iter: int, pareto_sampler: Callable, device=None,
+                 seed: Optional[int] = None, acq_factory: Optional[Callable] = None,
+                 hypercell_bounds_fn: Optional[Callable] = None):
+        if not callable(pareto_sampler):
+            raise TypeError("pareto_sampler(model, bounds, num_samples, target_num_points) must be callable")
+        self.estimation_type = estimation_type
+        self.num_pareto_samples = num_pareto_samples
+        self.num_pareto_points = num_pareto_points
+        self.num_restarts = num_restarts
+        self.raw_samples = raw_samples
+        self.batch_limit = batch_limit
+        self.max_iter = max_iter
+        self.pareto_sampler = pareto_sampler
+        self.device = device
+        self.seed = seed
+        # acq_factory(model, pareto_sets, pareto_fronts, hypercell_bounds, estimation_type, target_output_ix) ->
+        # acquisition: None builds the device acquisition (tests inject the CPU restatement to compare runs)
+        self.acq_factory = acq_factory
+        self.hypercell_bounds_fn = hypercell_bounds_fn
+
+    def _options(self) -> Dict:
+        opts = {"batch_limit": self.batch_limit, "maxiter": self.max_iter}
+        if self.seed is not None:
+            opts["seed"] = self.seed
+        return opts
+
+    def _samples(self, model, input_dim: int):
+        from .jes import compute_sample_box_decomposition
+
+        pareto_sets, pareto_fronts = self.pareto_sampler(model, _get_standard_bounds(input_dim),
+                                                         num_samples=self.num_pareto_samples,
+                                                         target_num_points=self.num_pareto_points)
+        fn = self.hypercell_bounds_fn or compute_sample_box_decomposition
+        return pareto_sets, pareto_fronts, fn(pareto_fronts)
+
+    def _acq(self, model, samples, target: Optional[int]):
+        from .jes import qLowerBoundMultiObjectiveJointEntropySearch
+
+        pareto_sets, pareto_fronts, hypercell_bounds = samples
+        if self.acq_factory is not None:
+            return self.acq_factory(model, pareto_sets, pareto_fronts, hypercell_bounds, self.estimation_type, target)
+        return qLowerBoundMultiObjectiveJointEntropySearch(model, pareto_sets, pareto_fronts, hypercell_bounds,
+                                                           estimation_type=self.estimation_type,
+                                                           target_output_ix=target, device=self.device)
+
+    def optimize_for_single_objective(self, model, costs: Union[Tensor, Sequence], input_dim: int,
+                                      **_unused_kwargs) -> Tuple[Tensor, int, Tensor]:
+        """One acquisition per objective on the same Pareto samples, best value per cost (:467-515)."""
+        from .discretekg import _as_model_state
+
+        samples = self._samples(model, input_dim)
+        candidates = []
+        for i in range(_as_model_state(model).num_outputs):
+            candidate_x, acq_value = optimize_acqf(acq_function=self._acq(model, samples, i),
+                                                   bounds=_get_standard_bounds(input_dim), q=1,
+                                                   num_restarts=self.num_restarts, raw_samples=self.raw_samples,
+                                                   options=self._options())
+            candidates.append((i, candidate_x.detach(), acq_value.detach()))
+        best_i, best_x, best_acqval_per_cost = self._choose_best_objective(candidates, costs)
+        return best_x, best_i, best_acqval_per_cost
+
+    def optimize_for_full_evaluation(self, model, input_dim: int, **_unused_kwargs) -> Tuple[Tensor, Tensor]:
+        """All outputs observed (:517-552)."""
+        samples = self._samples(model, input_dim)
+        candidate_x, acq_value = optimize_acqf(acq_function=self._acq(model, samples, None),
+                                               bounds=_get_standard_bounds(input_dim), q=1,
+                                               num_restarts=self.num_restarts, raw_samples=self.raw_samples,
+                                               options=self._options())
+        return candidate_x.detach(), acq_value.detach()
+
+    _choose_best_objective = staticmethod(DiscreteKgOptimisationSpec._choose_best_objective)

@@ -290,6 +290,58 @@ int dkg_pareto_nsga2(const dkg_output* outs, int m, int d, const double* lb, con
                      const dkg_nsga2_params* prm, const double* uniforms, double* X, double* F, int* rank,
                      double* crowd, void* work, size_t work_bytes, void* stream);
 
+/* ---- Lower-bound joint entropy search (JES-LB / LB2, Tu et al. 2022) on the device (dkg_jes.hip) ------------
+ * The reference's qLowerBoundMultiObjectiveJointEntropySearch (modules/acquisition/joint_entropy_search.py:291-526)
+ * for q = 1 with estimation_type "LB" / "LB2" and its target_output_ix: per candidate x
+ *   acq(x) = H_0(x) - (1 / P) sum_p H_p(x)
+ * with H_0 the entropy of the model's noisy predictive at x (:402-425; all outputs, or the target alone) and H_p
+ * the entropy bound of _compute_entropy_upper_bound (:596-732) on the moments of the model conditioned on Pareto
+ * sample p (:365-376, 428-470) over that sample's boxes.  All objectives are maximised.  DESIGN.md 8d states the
+ * formulas.  A "state" is one model: state 0 the model itself, state p + 1 the model conditioned on sample p;
+ * each is m dkg_output structs of which n, kernel, outputscale, noise, mean_constant, y_mean, y_std,
+ * inv_lengthscale, train_x, alpha and root_frag are read (dkg_prepare_outputs' caches; disc_* are not read).
+ * Limits (DKG_ERR_UNSUPPORTED beyond them): m <= DKG_MAX_OUTPUTS, d <= DKG_MAX_DIM, n <= 1024 per state-output,
+ * P <= DKG_JES_MAX_SAMPLES samples, J <= DKG_JES_MAX_BOXES boxes per sample, max_B <= DKG_JES_MAX_CANDIDATES. */
+#define DKG_JES_MAX_SAMPLES 64
+#define DKG_JES_MAX_BOXES 4096
+#define DKG_JES_MAX_CANDIDATES 65536
+/* Bytes of the host plan (caller memory, kept unchanged while the plan is in use). */
+size_t dkg_jes_plan_bytes(void);
+/* Bytes of device scratch a plan for up to max_B candidates needs: the state table, and per (state, output,
+ * candidate) the model-space mean, |K(x, X) R|^2 and their d x-derivatives.  0 for sizes dkg_jes_init refuses. */
+size_t dkg_jes_workspace(int m, int P, int d, int J, int max_B);
+/* A plan: everything an evaluation needs besides the candidates.
+ *   states       : host array of (P + 1) m structs, state s output i at s m + i; copied into host_plan and
+ *                  uploaded once into the workspace on `stream` (the device buffers they point to must outlive
+ *                  the plan)
+ *   bounds       : device [P][2][J][m], the hypercell bounds (hypercell_bounds of :66-71; [.][0] lower, [.][1]
+ *                  upper corners, untransformed output space).  Lower bounds may be -1e10 and a sample with
+ *                  fewer boxes is padded with zero-width boxes [0, 0] (jes_sample_pareto.py:243-245).  Read at
+ *                  every evaluation, not copied.
+ *   target       : -1 all outputs observed, t in [0, m) the reference's target_output_ix
+ *   only_diagonal: 0 "LB", non-zero "LB2" (:232-250)
+ *   workspace    : device scratch of dkg_jes_workspace() bytes, owned by the plan while it is in use
+ * DKG_ERR_ARG for NULL pointers, sizes < 1, a target outside [-1, m), n < 1 or an unknown kernel id;
+ * DKG_ERR_UNSUPPORTED beyond the limits above; DKG_ERR_WORKSPACE for a short workspace.  The arguments are checked
+ * before any HIP call; nothing synchronises. */
+int dkg_jes_init(const dkg_output* states, int m, int P, int d, const double* bounds, int J, int target,
+                 int only_diagonal, int max_B, void* workspace, size_t workspace_bytes, void* host_plan, void* stream);
+/* acq[b] for B <= max_B candidates x (device [B][d], model inputs) and, when dacq_dx is not NULL,
+ * dacq_dx[b*d + j] = d acq[b] / d x[b*d + j] (device [B][d]): what autograd gives optimize_acqf through
+ * qLowerBoundMultiObjectiveJointEntropySearch.forward (:512-526, acquisition_optimisation_strategy.py:493-508).
+ * Wherever one of the reference's clamps binds, that term's derivative is 0, as clamp_min / clamp_max give.
+ *   moments_out (nullable): device [3][(P + 1) m][B], untransformed space, per (state, output, candidate):
+ *     [0] the posterior mean, [1] v = max(var, eps), [2] tau = max(max(var + noise, eps) - v, eps)
+ *     (eps = 2^-52, :403, 440-461); state 0: [1] holds var + noise (the argument of H_0) and [2] is 0.
+ * Two launches whatever P and m are: the moments of every (state, output) over 16-candidate tiles
+ * (v_mfma_f64_16x16x4_f64 against root_frag; K(x, X) R is never written to memory), then one workgroup per
+ * candidate for the entropies and the chain rule to dx.  Stream ordered, nothing synchronises.  Deterministic:
+ * every sum runs in a fixed order without atomics, so two calls give the same bits and a candidate's result has
+ * the same bits whatever B is and whichever row holds it.  DKG_ERR_ARG for NULL pointers, an uninitialised plan
+ * or B outside [1, max_B], checked before any HIP call. */
+int dkg_jes_forward(const void* host_plan, const double* x, int B, double* acq, double* dacq_dx, double* moments_out,
+                    void* stream);
+
 /* Bytes of scratch dkg_forward needs for (m outputs, N points, B candidates, S weights). */
 size_t dkg_forward_workspace(const dkg_output* outs, int m, int N, int B, int S);
 
