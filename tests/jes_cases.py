@@ -13,6 +13,10 @@ point of output 0.
 
 Condition on the inputs (asserted here, on the reference alone): every (candidate, sample) has
 W = sum_j W_j >= 1e-3; the seeds below were moved until it held.
+
+Two sets: CASES (families, noise levels, Standardize on and off; the reference-side spreads that set the bounds
+of tests/test_gpu_jes.py are taken over these alone) and SHAPE_CASES (the shapes at which the kernels' loops
+repeat and their limits; see the comment there).  ``problem`` and ``reference`` take an id of either.
 """
 
 from __future__ import annotations
@@ -42,7 +46,48 @@ CASES = {
 OPT_CASE = "m2-d2-opt"
 EXTRA_CASES = {OPT_CASE: dict(m=2, d=2, ns=(13, 21), fam=("M52", "M32"), noise=1e-2, std=True, ks=(1, 3, 5), J=5, B=4,
                               seed=15)}
+# The shapes at which the kernels' loops repeat (csrc/dkg_jes.hip), kept apart from CASES: the recorded spreads
+# are taken over CASES alone, and test_jes_host.py asserts that none of these exceeds them.  The moments stage
+# gives wave w the column tiles 8 s + (s odd ? 7 - w : w) of Q, T = pad16(n) / 16 of them; the entropy stage
+# gives wave w the states w, w + 4, ... of the P + 1 and walks the boxes in rounds of 64.  All with noise 1e-2
+# and Standardize; Matern-1/2 outputs keep n + max(ks) + 1 <= 25 (the oracle's exact-cdist rule), so the large-n
+# outputs are of the other families.  ``overlap``: every sample's boxes stated twice, so that sum_j W_j doubles
+# and the clamp W = min(sum_j W_j, 1) binds for most (candidate, sample) pairs and not for the others.
+SHAPE_CASES = {
+    # state 0 has T = 8, the conditioned states T = 9 (tile 8 is wave 7's alone, at s = 1); P = 4: wave 0 takes
+    # two states; d = 3 in DM = 4; B = 16: no clamped candidate row
+    "n127-P4-d3": dict(m=1, d=3, ns=(127,), fam=("M52",), noise=1e-2, std=True, ks=(3, 3, 3, 3), J=1, B=16, seed=31),
+    # 253 + (1, 2, 3 | 4, 5) rows: T = 16 | 17 (tile 16 is wave 0's alone, at s = 2); 139 + 5 = 144 rows exactly
+    # (T = 9 with no padded row); 8 states: two full rounds; d = 4 fills DM = 4
+    "n253-P7-d4": dict(m=2, d=4, ns=(253, 139), fam=("RBF", "M32"), noise=1e-2, std=True, ks=(3, 5, 1, 4, 2, 5, 3),
+                       J=6, B=17, seed=33),
+    # 1019 + 5 = 1024 rows: every s on every wave, 32 rounds of the slab fill, the largest LDS request
+    "n1019-k5": dict(m=1, d=2, ns=(1019,), fam=("M32",), noise=1e-2, std=True, ks=(5,), J=1, B=5, seed=31),
+    # M = 8 with three padded outputs; d = 9 in DM = 16; J = 64: one full round, no clamped lane
+    "m5-d9-J64": dict(m=5, d=9, ns=(20, 31, 17, 45, 27), fam=ALL_FAMILIES, noise=1e-2, std=True, ks=(3, 5, 1, 2),
+                      J=64, B=16, seed=31),
+    # M = 8 with one padded output; d = 8 fills DM = 8; J = 65: a second round of one lane
+    "m7-d8-J65": dict(m=7, d=8, ns=(20, 31, 17, 45, 27, 38, 18), fam=("RBF", "M32", "M12", "M52"), noise=1e-2,
+                      std=True, ks=(3,), J=65, B=5, seed=31),
+    # M = 4 exactly; d = 16 fills DM = 16 (17 slab passes); 10 states: three rounds; J = 129: three box rounds
+    "m4-d16-P9-J129": dict(m=4, d=16, ns=(33, 48, 17, 61), fam=ALL_FAMILIES, noise=1e-2, std=True,
+                           ks=(3, 5, 1, 2, 4, 3, 5, 2, 4), J=129, B=5, seed=31),
+    # DKG_JES_MAX_SAMPLES: 65 states
+    "m1-P64": dict(m=1, d=1, ns=(13,), fam=("M52",), noise=1e-2, std=True, ks=(1, 2, 3, 4) * 16, J=1, B=2, seed=31),
+    # DKG_JES_MAX_BOXES: 64 box rounds
+    "m2-J4096": dict(m=2, d=1, ns=(13, 21), fam=("M52", "M32"), noise=1e-2, std=True, ks=(3,), J=4096, B=2, seed=31),
+    # sum_j W_j on both sides of 1 (J = 6 stated twice: 12 boxes)
+    "m2-overlap": dict(m=2, d=2, ns=(13, 21), fam=("M52", "M32"), noise=1e-2, std=True, ks=(1, 3, 5), J=6, B=17,
+                       seed=33, overlap=True),
+}
 ESTIMATORS = ("LB", "LB2")
+
+
+def case(cid: str) -> dict:
+    for cases in (CASES, SHAPE_CASES, EXTRA_CASES):
+        if cid in cases:
+            return cases[cid]
+    raise KeyError(cid)
 
 
 def targets_of(m: int):
@@ -85,7 +130,7 @@ def problem(cid: str):
     """-> (state, pareto_sets, pareto_fronts, bounds [P, 2, J, m], X [B, d])."""
     from dkg_amd.model import ModelListGPState, SingleTaskGPState
 
-    c = CASES[cid] if cid in CASES else EXTRA_CASES[cid]
+    c = case(cid)
     state, _, _, X = grad_case(c["m"], c["d"], c["ns"], c["fam"], 4, 2, c["B"], c["seed"], noise=c["noise"])
     if not c["std"]:
         state = ModelListGPState(*[SingleTaskGPState(o.train_x, o.train_y, o.lengthscale, o.outputscale, o.noise,
@@ -112,6 +157,8 @@ def problem(cid: str):
         fronts.append(pf)
     bounds = make_bounds(fronts, [o.y_std for o in state.models], c["J"])
     assert bounds.shape[2] == max(c["J"], 1), (cid, bounds.shape)
+    if c.get("overlap"):
+        bounds = torch.cat([bounds, bounds], dim=2)
     X = X.clone()
     X[0] = sets[0][0]
     if X.shape[0] > 1:

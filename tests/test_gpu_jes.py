@@ -10,7 +10,12 @@ floor; the factor 4 covers the device's different association of the same sums).
 plus 4 x SPREAD_GRAD, measured the same way on the autograd gradient.  Both spreads are measured on the CPU
 (test_jes_host.py checks the constants against a fresh measurement) and are set by the noise = 1e-8 case.
 
-Measured on MI355X (worst over the cases): DEVICE_WORST below and DESIGN.md 8d.
+The same three tests and bounds run over jes_cases.SHAPE_CASES: the shapes at which the kernels' loops repeat
+(more than 8 column tiles of Q per workgroup, up to the 64 of n = 1024; more states than waves, up to 65; the
+d buckets 4 and 16; m = 4, 5, 7; 64, 65, 129 and 4096 boxes; sum_j W_j on both sides of 1).  The spreads stay
+those of CASES.  Bit tests cover a plan that grows, a full candidate tile, and the candidate limit.
+
+Measured on MI355X (worst over the cases): DEVICE_WORST and DEVICE_WORST_SHAPES below and DESIGN.md 8d.
 """
 
 import functools
@@ -33,10 +38,16 @@ RTOL = 1e-6
 # moments |d mu| / bound, |d v| / bound; entropy stage alone |d acq|; end to end |d acq|; gradient |d g|
 DEVICE_WORST = {"mu_ratio": 5.3e-6, "v_ratio": 4.3e-7, "stage": 2.7e-9, "end_to_end": 3.1e-9, "grad": 3.9e-11}
 
-CASE_IDS = list(jes_cases.CASES)
+# the same over jes_cases.SHAPE_CASES, asserted with the bounds above (their own reference-side spreads, at most
+# 1.3e-13 and 1.3e-12, set none: test_jes_host.py).  mu and the gradient from n1019-k5, v from n127-P4-d3, the values from m7-d8-J65
+DEVICE_WORST_SHAPES = {"mu_ratio": 1.65e-5, "v_ratio": 3.0e-7, "stage": 1.42e-14, "end_to_end": 1.55e-13,
+                       "grad": 1.15e-12}
+
+ALL_CASES = {**jes_cases.CASES, **jes_cases.SHAPE_CASES}
+CASE_IDS = list(ALL_CASES)
 COMBOS = [(cid, est, t) for cid in CASE_IDS for est in jes_cases.ESTIMATORS
-          for t in jes_cases.targets_of(jes_cases.CASES[cid]["m"])]
-M12_CASES = {cid for cid, c in jes_cases.CASES.items() if "M12" in c["fam"]}
+          for t in jes_cases.targets_of(ALL_CASES[cid]["m"])]
+M12_CASES = {cid for cid, c in ALL_CASES.items() if "M12" in c["fam"]}
 
 
 def _id(v):
@@ -151,6 +162,81 @@ def test_bits():
         a = device_result(cid, "LB", t)[0]
         b = device_result(cid, "LB2", t)[0]
         assert bool(((a - b).abs() <= RTOL * a.abs() + 4 * SPREAD_VALUE).all()), t
+
+
+def _fresh(cid, est="LB", target=None):
+    from dkg_amd.jes import qLowerBoundMultiObjectiveJointEntropySearch as JES
+
+    state, sets, fronts, bounds, X = jes_cases.problem(cid)
+    return JES(state, sets, fronts, bounds, estimation_type=est, target_output_ix=target, device=DEV), X
+
+
+def test_bits_do_not_change_when_the_plan_grows():
+    """A new acquisition: 3 candidates (a plan for 16), then 17 (a new plan for 32, another workspace carve and
+    row pitch), then the 3 again on the grown plan."""
+    acq, X = _fresh("n253-P7-d4")
+    assert X.shape[0] == 17
+    v3, g3 = acq.value_and_grad_host(X[:3])
+    assert acq._plan.max_B == 16
+    v17, g17 = acq.value_and_grad_host(X)
+    assert acq._plan.max_B == 32
+    w3, h3 = acq.value_and_grad_host(X[:3])
+    assert acq._plan.max_B == 32
+    assert torch.equal(v3, w3) and torch.equal(g3, h3)
+    assert torch.equal(v3, v17[:3]) and torch.equal(g3, g17[:3])
+    # and the cached acquisition of the oracle tests, whose plan began at 32
+    v, g, _ = device_result("n253-P7-d4", "LB", None)
+    assert torch.equal(v, v17) and torch.equal(g, g17)
+
+
+def test_bits_of_a_full_tile_are_those_of_its_candidates_alone():
+    """B = 16: no row of the moments stage's tile is a clamped repeat; against 16 calls with B = 1, where 15 are."""
+    cid = "n127-P4-d3"
+    X = jes_cases.problem(cid)[4]
+    assert X.shape[0] == 16
+    for est, t in (("LB", None), ("LB2", 0)):
+        acq = acquisition(cid, est, t)
+        v16, g16 = acq.value_and_grad_host(X)
+        for b in range(16):
+            vb, gb = acq.value_and_grad_host(X[b:b + 1])
+            assert torch.equal(vb, v16[b:b + 1]) and torch.equal(gb, g16[b:b + 1]), (est, t, b)
+
+
+def test_grid_edge_of_the_candidates():
+    """DKG_JES_MAX_CANDIDATES = 65536 candidates in one call (4096 tiles x 8 state-outputs; 65536 workgroups of
+    the entropy stage): the 40 candidates of the case over and over, every copy with the bits of the B = 40 call.
+    One more candidate is refused by dkg_jes_init, before any launch."""
+    from dkg_amd import UnsupportedError, _lib
+
+    cid = "m2-d2-P3-J6-noise1e-8"
+    acq, X = _fresh(cid)
+    B = _lib.DKG_JES_MAX_CANDIDATES
+    with torch.no_grad():
+        v40 = acq(X.unsqueeze(1))
+        assert torch.equal(v40, device_result(cid, "LB", None)[0])
+        reps = -(-B // 40)
+        big = acq(X.repeat(reps, 1)[:B].unsqueeze(1))
+        assert acq._plan.max_B == B and big.shape == (B,)
+        assert torch.equal(big, v40.repeat(reps)[:B])
+        plan = acq._plan
+        with pytest.raises(UnsupportedError, match="dkg_jes_init.*candidates"):
+            acq(X.repeat(reps, 1)[:B + 1].unsqueeze(1))
+        assert acq._plan is plan
+
+
+def test_more_than_1024_training_rows_are_refused():
+    """A model of 1024 points is served (n1019-k5 reaches 1024 rows by conditioning); one Pareto point more makes
+    the conditioned state 1025 rows, which the preparation of that state refuses at construction, ahead of
+    dkg_jes_init's own check of n (test_jes_host.py)."""
+    from dkg_amd import UnsupportedError, compute_sample_box_decomposition
+    from dkg_amd.jes import qLowerBoundMultiObjectiveJointEntropySearch as JES
+    from helpers import grad_case
+
+    state, _, _, X = grad_case(1, 1, (1024,), ("M52",), 4, 2, 2, 31, noise=1e-2)
+    front = torch.tensor([[1.0]], dtype=torch.double)
+    with pytest.raises(UnsupportedError, match="1025"):
+        acq = JES(state, [X[:1]], [front], compute_sample_box_decomposition([front]), device=DEV)
+        acq.value_and_grad_host(X)
 
 
 def test_errors_on_the_device():

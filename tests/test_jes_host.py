@@ -203,6 +203,51 @@ def test_cases_cover_the_shapes_and_meet_the_condition():
         jes_cases.reference(cid)                                         # asserts W >= 1e-3 for every estimator
 
 
+def _tiles(cid, conditioned=True):
+    """The column-tile counts pad16(rows) // 16 of the case's state-outputs: the conditioned ones, or state 0's."""
+    ns = [o.num_train for o in jes_cases.problem(cid)[0].models]
+    ks = jes_cases.SHAPE_CASES[cid]["ks"] if conditioned else (0,)
+    return {(n + k + 15) // 16 for n in ns for k in ks}
+
+
+def test_shape_cases_reach_the_loops_they_promise():
+    sc = jes_cases.SHAPE_CASES
+    cs = sc.values()
+    assert not set(sc) & (set(jes_cases.CASES) | set(jes_cases.EXTRA_CASES))
+    assert {c["m"] for c in cs} == {1, 2, 4, 5, 7} and {c["d"] for c in cs} == {1, 2, 3, 4, 8, 9, 16}
+    assert {c["J"] for c in cs} == {1, 6, 64, 65, 129, _lib.DKG_JES_MAX_BOXES}
+    assert {len(c["ks"]) for c in cs} == {1, 3, 4, 7, 9, _lib.DKG_JES_MAX_SAMPLES} and {c["B"] for c in cs} == {2, 5, 16, 17}
+    assert all(c["noise"] == 1e-2 and c["std"] for c in cs)
+    # the moments stage's column tiles: 8 | 9 (s = 1 on wave 7 alone), 16 and 17 (s = 2 on wave 0 alone), 64 (all)
+    assert _tiles("n127-P4-d3", False) == {8} and _tiles("n127-P4-d3") == {9}
+    assert _tiles("n253-P7-d4") == {16, 17, 9}
+    assert _tiles("n1019-k5") == {64} and _tiles("n1019-k5", False) == {64}
+    c = sc["n253-P7-d4"]
+    assert 144 in {n + k for n in c["ns"] for k in c["ks"]}                # a conditioned output with no padded row
+
+
+@pytest.mark.parametrize("cid", list(jes_cases.SHAPE_CASES))
+def test_shape_case_meets_the_condition_and_sets_no_bound(cid):
+    import test_gpu_jes as t
+
+    c = jes_cases.SHAPE_CASES[cid]
+    state, sets, fronts, bounds, X = jes_cases.problem(cid)
+    assert [o.num_train for o in state.models] == list(c["ns"]) and bounds.shape[0] == len(c["ks"])
+    assert bounds.shape[2] == (2 if c.get("overlap") else 1) * c["J"] and X.shape == (c["B"], c["d"])
+    # Matern-1/2 outputs stay on torch.cdist's exact path in the oracle (jes_oracle.CHUNK)
+    assert all(o.num_train + max(c["ks"]) + 1 <= 25 for o in state.models if (o.kernel, o.nu) == ("matern", 0.5))
+    assert torch.equal(X[0], sets[0][0]) and torch.equal(X[1], state.models[0].train_x[3])
+    ref = jes_cases.reference(cid)                                   # asserts W >= 1e-3 for every estimator
+    # no shape case sets the bounds of test_gpu_jes.py
+    sv, sg = jes_cases.spreads(cid)
+    print(f"{cid}: reference-side spread: value {sv:.3g}, gradient {sg:.3g}")
+    assert sv <= t.SPREAD_VALUE and sg <= t.SPREAD_GRAD, (cid, sv, sg)
+    _, Wsum = jes_oracle.acq_from_moments(bounds, *ref["moments"], None, False, return_w=True)
+    if c.get("overlap"):                                             # both arms of W = min(sum_j W_j, 1)
+        assert bool((Wsum > 1.0).any()) and bool((Wsum < 1.0).any())
+        assert int((Wsum > 1.0 + 1e-9).sum()) >= 5 and int((Wsum < 1.0 - 1e-9).sum()) >= 5
+
+
 def test_recorded_spreads_cover_a_fresh_measurement():
     import test_gpu_jes as t
 
