@@ -398,6 +398,13 @@ __device__ __forceinline__ double sgpr_f64(double v) {
                           __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
+// A wave-uniform double held in SGPRs at this point of the program: an empty asm statement that the optimiser
+// moves no load across, so the load of v stays a scalar load issued here, whichever lanes use the value.
+__device__ __forceinline__ double pin_sgpr_f64(double v) {
+  int hi = __double2hiint(v), lo = __double2loint(v);
+  asm volatile("" : "+s"(hi), "+s"(lo));
+  return __hiloint2double(hi, lo);
+}
 
 // Cross-row combine after DKG_BUTTERFLY_ROW: the four row values by v_readlane
 // (scalar registers, no LDS round trip as the ds_bpermute steps 16/32 take),

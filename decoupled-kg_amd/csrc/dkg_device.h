@@ -1392,6 +1392,9 @@ __device__ __forceinline__ void pair_coefs(const double* wrow, int m, bool full,
                                            const double (&ymu)[M], const double (&nz)[M], const double (&sv)[M],
                                            double (&w)[M], double (&wa)[M], double (&wb)[M], double& a_off,
                                            double& den) {
+  // No contraction beyond the fmas written out: the forward envelope evaluates this in one wave per workgroup,
+  // the other kernels per wave, and every copy must round the same way.
+#pragma clang fp contract(off)
   a_off = 0.0;
   den = 0.0;
 #pragma unroll
@@ -1441,9 +1444,10 @@ struct EnvLds {
   // record -1 lands here)
   int lmu;   // [SLp]       mu_D records [N][rec]
   int lcv;   // [SLp]       the candidate's covariance records [N][rec]
-  int lw;    // [S m]       the weights (rounded up to a 16-byte piece)
+  int lw;    // [S m]       the weights (rounded up to a 16-byte piece; the staged forward leaves it unused)
   int skg;   // [S]         KG_j of the group's pairs, summed in j order (rounded up likewise)
-  int sbuf;  // [SW][2][LC] per wave: the survivor list's slopes and intercepts
+  int sbuf;  // [SW][2][LC] per wave: the survivor list's slopes and intercepts (staged forward: until the wave's
+             // filter, the head of each list holds its pair's coefficient row, envelope_body COEF1)
   // forward
   int cbuf;  // streaming: the quickhull refinement's vertex arrays [SW][VREG], or (stream_staged) the four
              // staged chunk buffers [4][staged_chunk_len], whose room the refinement reuses after the passes
@@ -1646,19 +1650,37 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
   // covariance stage, mean from the cross stage): lane i of wave 0 loads output i
   double pp[NPP] = {1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   double g_gm[M], g_il[M], g_x = 0.0;  // GRAD: staged to LDS after the wait
+  // pairs j0 .. j1-1 of the candidate, one per wave (gridDim.y = ceil(S / SW), envelope_geometry)
+  const int j0 = g * SW, j1 = min(S, j0 + SW);
+  // COEF1 (the staged forward): the line coefficients of the workgroup's pairs are evaluated once, by wave 0
+  // (lane p: pair j0 + p) while the staging DMAs are in flight, and handed to the pairs' waves through LDS
+  // (per pair wa[M] | wb[M] | a_off | line 0's a, b), instead of by all 64 lanes of each wave after the
+  // barrier.  The hand-over takes no LDS of its own: pair p's row lies at the head of wave p's survivor list
+  // (sbuf, 2 LC doubles per wave), which the wave first writes in its filter, after it has read the row into
+  // SGPRs; so the kernels' static and dynamic LDS, and what fits a CU, stay what they were.  pair_coefs reads only the weights, the outputs' constants and the candidate's variance: none of
+  // them staged data, none touched by the coincidence fix-up below (which changes line 0 alone: the pairs'
+  // waves rebuild it then).  The inputs are loaded with the first batch, all by scalar loads (uniform
+  // addresses: they are not queued on vmcnt with the DMAs, so wave 0 need not wait for the staged data), row
+  // p of the weights then selected into lane p; lanes without a pair hold the last pair's and write nothing.
+  constexpr bool COEF1 = !GRAD && !STREAM && !HO;
+  constexpr int ENV_MAX_WAVES = 512 / 64;  // (the kernels' launch bounds)
+  constexpr int NPC = 2 * M + 3;
+  static_assert(NPC <= 2 * ENV_CAP, "a pair's coefficient row fits its wave's survivor list");
   if (threadIdx.x < m) {
-    const dkg_output* o = &P->o[threadIdx.x];
-    pp[0] = o->y_std;
-    pp[1] = o->y_mean;
-    pp[2] = o->noise;
-    pp[3] = o->outputscale;
-    if constexpr (!HO) {
+    if constexpr (!COEF1) {
+      const dkg_output* o = &P->o[threadIdx.x];
+      pp[0] = o->y_std;
+      pp[1] = o->y_mean;
+      pp[2] = o->noise;
+      pp[3] = o->outputscale;
+    }
+    if constexpr (!HO && !COEF1) {
       pp[4] = var_all[(size_t)threadIdx.x * bpad + b];
       pp[5] = mux_all[(size_t)threadIdx.x * bpad + b];
       pp[6] = pp[5];
       pp[7] = pp[4];
     }
-    if constexpr (GRAD) s_kind[threadIdx.x] = o->kernel;
+    if constexpr (GRAD) s_kind[threadIdx.x] = P->o[threadIdx.x].kernel;
   }
   const double* wsrc = wts;
   if constexpr (!STREAM) {
@@ -1679,7 +1701,43 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
       }
     }
   }
-  for (int e = threadIdx.x; e < S * m; e += blockDim.x) lw[e] = wsrc[e];
+  if constexpr (!COEF1)  // (COEF1: wave 0 reads its pairs' rows from global memory; the lw region stays unused)
+    for (int e = threadIdx.x; e < S * m; e += blockDim.x) lw[e] = wsrc[e];
+  // (after the DMAs are issued: scalar loads of kernel-argument arrays and plan fields are not re-read for them)
+  double c_w[M], c_ysd[M], c_ymu[M], c_nz[M], c_sv[M], c_mx[M];
+  if constexpr (COEF1) {
+    if (wave == 0) {
+#pragma unroll
+      for (int i = 0; i < M; ++i) {
+        const bool live = i < m;
+        const int ic = min(i, m - 1);  // (unconditional loads; outputs i >= m: the constants of the per-wave path)
+        const dkg_output* o = &P->o[ic];
+        const double ysd_i = o->y_std, ymu_i = o->y_mean, nz_i = o->noise;
+        const double sv_i = var_all[(size_t)ic * bpad + b], mx_i = mux_all[(size_t)ic * bpad + b];
+        c_ysd[i] = live ? ysd_i : 1.0;
+        c_ymu[i] = live ? ymu_i : 0.0;
+        c_nz[i] = live ? nz_i : 0.0;
+        c_sv[i] = live ? sv_i : 0.0;
+        c_mx[i] = live ? mx_i : 0.0;
+        c_w[i] = 0.0;
+      }
+      double wr[ENV_MAX_WAVES][M];  // every row in one scalar-load batch, then pinned: no load under a lane mask
+#pragma unroll
+      for (int p = 0; p < ENV_MAX_WAVES; ++p) {
+        const double* wrow = wts + (size_t)min(j0 + p, j1 - 1) * m;
+#pragma unroll
+        for (int i = 0; i < M; ++i) wr[p][i] = wrow[min(i, m - 1)];
+      }
+#pragma unroll
+      for (int p = 0; p < ENV_MAX_WAVES; ++p) {
+#pragma unroll
+        for (int i = 0; i < M; ++i) {
+          const double v = pin_sgpr_f64(wr[p][i]);
+          c_w[i] = (lane_k >= p) ? v : c_w[i];
+        }
+      }
+    }
+  }
   // candidate b's coincidence mark (the covariance stage's; loaded with the first batch, used after the wait)
   int dupk = DUP_NONE;
   if constexpr (!HO) dupk = dupv[b];
@@ -1689,13 +1747,17 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
   constexpr bool HINT = !GRAD && !STREAM && !HO;
   if constexpr (HINT) {
     if (P->itop != nullptr) {
+      // (plan data, written at plan build only: read through the constant address space, so the loads are
+      // scalar and no vector-memory wait ahead of the staging barrier stands behind the DMAs)
       const int jh = min(g * SW + wave, S - 1);
-      hA1 = P->itop[jh];
-      hk1 = P->itopk[2 * jh];
-      hc1 = P->itopk[2 * jh + 1];
+      const auto* itop_c = (const __attribute__((address_space(4))) double*)P->itop;
+      const auto* itopk_c = (const __attribute__((address_space(4))) int*)P->itopk;
+      hA1 = itop_c[jh];
+      hk1 = itopk_c[2 * jh];
+      hc1 = itopk_c[2 * jh + 1];
     }
   }
-  if (threadIdx.x < m) {
+  if (!COEF1 && threadIdx.x < m) {  // (COEF1: s_pp holds the coincident record alone, written by the fix-up)
 #pragma unroll
     for (int q = 0; q < (HO ? 4 : NPP); ++q) s_pp[threadIdx.x * NPP + q] = pp[q];
   }
@@ -1740,8 +1802,30 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
     }
   };
   if constexpr (!STREAM) pad_lines(max(N * MP, SLd), pad_end);
-  // pairs j0 .. j1-1 of the candidate, one per wave (gridDim.y = ceil(S / SW), envelope_geometry)
-  const int j0 = g * SW, j1 = min(S, j0 + SW);
+  if constexpr (COEF1) {
+    if (wave == 0) {
+      double w[M], wa[M], wb[M];
+      double a_off, den;
+      pair_coefs<M>(c_w, m, full, target, c_ysd, c_ymu, c_nz, c_sv, w, wa, wb, a_off, den);
+      double a0 = a_off, b0 = 0.0;  // line 0 from the candidate's own posterior (no coincidence)
+#pragma unroll
+      for (int i = 0; i < M; ++i) {
+        a0 = fma(wa[i], c_mx[i], a0);
+        b0 = fma(wb[i], c_sv[i], b0);
+      }
+      if (lane_k < j1 - j0) {
+        double* row = sbuf + (size_t)lane_k * 2 * LC;
+#pragma unroll
+        for (int i = 0; i < M; ++i) {
+          row[i] = wa[i];
+          row[M + i] = wb[i];
+        }
+        row[2 * M] = a_off;
+        row[2 * M + 1] = a0;
+        row[2 * M + 2] = b0;
+      }
+    }
+  }
   if (!GRAD) KST(st, 2);  // GRAD stamps: 2 preamble done, 3 filter, 4 hull, 5 gradient flush (first pair)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -1837,6 +1921,15 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
 #pragma unroll
   for (int i = 0; i < M; ++i) {
     const bool live = i < m;
+    if constexpr (COEF1) {  // only a coincident candidate's line 0 is rebuilt per wave (below)
+      ysd[i] = 1.0;
+      ymu[i] = nz[i] = os[i] = sv[i] = mx0[i] = l0m[i] = l0v[i] = 0.0;
+      if (dupk != DUP_NONE) {
+        l0m[i] = sgpr_f64(live ? s_pp[i * NPP + 6] : 0.0);
+        l0v[i] = sgpr_f64(live ? s_pp[i * NPP + 7] : 0.0);
+      }
+      continue;
+    }
     // workgroup-uniform: kept in SGPRs across the pair loop
     ysd[i] = sgpr_f64(live ? s_pp[i * NPP + 0] : 1.0);
     ymu[i] = sgpr_f64(live ? s_pp[i * NPP + 1] : 0.0);
@@ -2028,7 +2121,22 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
     // ---- line coefficients (wave uniform; shared with lines_export_kernel)
     double w[M], wa[M], wb[M];
     double a_off, den;
-    pair_coefs<M>(lw + j * m, m, full, target, ysd, ymu, nz, sv, w, wa, wb, a_off, den);
+    double a0l = 0.0, b0l = 0.0;  // COEF1: line 0
+    if constexpr (COEF1) {  // wave 0's, before the staging barrier (w and den: the gradient's only)
+      const double* row = sb;
+#pragma unroll
+      for (int i = 0; i < M; ++i) {
+        w[i] = 0.0;
+        wa[i] = row[i];
+        wb[i] = row[M + i];
+      }
+      a_off = row[2 * M];
+      den = 0.0;
+      a0l = row[2 * M + 1];
+      b0l = row[2 * M + 2];
+    } else {
+      pair_coefs<M>(lw + j * m, m, full, target, ysd, ymu, nz, sv, w, wa, wb, a_off, den);
+    }
 #pragma unroll
     for (int i = 0; i < M; ++i) {  // wave-uniform: SGPRs, not VGPRs, while the lines are live
       w[i] = sgpr_f64(w[i]);
@@ -2037,6 +2145,21 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
     }
     a_off = sgpr_f64(a_off);
     den = sgpr_f64(den);
+    // line 0: the candidate itself (discretekg.py:182-183), or the record it coincides with
+    auto line0 = [&](double& a, double& bb) __attribute__((always_inline)) {
+      a = a_off;
+      bb = 0.0;
+#pragma unroll
+      for (int i = 0; i < M; ++i) {
+        a = fma(wa[i], l0m[i], a);
+        bb = fma(wb[i], l0v[i], bb);
+      }
+    };
+    if constexpr (COEF1) {
+      if (dupk != DUP_NONE) line0(a0l, b0l);  // (uniform) the same chains over the record's components
+      a0l = sgpr_f64(a0l);
+      b0l = sgpr_f64(b0l);
+    }
     // ---- lines: slot t of lane l is line k = l + 64 t (k = 0: the candidate).
     // Branch-free bodies (one LDS read stream per array, no per-slot waits):
     // unused output slots read output 0 with a zero weight.  Rebuilt from the
@@ -2116,12 +2239,8 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
         }
       }
       {
-        double a = a_off, bb = 0.0;  // line 0: the candidate itself (discretekg.py:182-183)
-#pragma unroll
-        for (int i = 0; i < M; ++i) {
-          a = fma(wa[i], l0m[i], a);
-          bb = fma(wb[i], l0v[i], bb);
-        }
+        double a = a0l, bb = b0l;
+        if constexpr (!COEF1) line0(a, bb);
         la[0] = (lane == 0) ? a : la[0];
         lb[0] = (lane == 0) ? bb : lb[0];
       }
@@ -2430,12 +2549,8 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
       // k >= 1 do not depend on the candidate, so the plan keeps each scalarisation's largest (Plan::itop)
       TopHint hint{false, 0.0, 0.0};
       if (HINT && flat_ok && P->itop != nullptr) {
-        double a0 = a_off, b0 = 0.0;
-#pragma unroll
-        for (int i = 0; i < M; ++i) {
-          a0 = fma(wa[i], l0m[i], a0);
-          b0 = fma(wb[i], l0v[i], b0);
-        }
+        double a0 = a0l, b0 = b0l;
+        if constexpr (!COEF1) line0(a0, b0);
         const double A1 = hA1;
         const int k1 = hk1, c1 = hc1;
         if (a0 > A1) {
