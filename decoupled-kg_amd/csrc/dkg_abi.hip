@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <vector>
 
 #include "dkg_kernels.h"
 
@@ -1045,6 +1046,39 @@ int dkg_debug_plan_envelope(const void* host_plan, int out[4]) {
   out[1] = h.stream ? 1 : 0;
   out[2] = h.sw;
   out[3] = h.split;
+  return 0;
+}
+
+int dkg_debug_plan_qx32(const void* host_plan, int output, int B, float* host_out, void* stream) {
+  if (!host_plan || !host_out) return fail(DKG_ERR_ARG, "dkg_debug_plan_qx32: NULL pointer");
+  const Plan& h = *static_cast<const Plan*>(host_plan);
+  if (!h.f32) return fail(DKG_ERR_UNSUPPORTED, "dkg_debug_plan_qx32: the plan has no fp32 Q_X (DKG_PLAN_F32 only)");
+  if (output < 0 || output >= h.m || B < 1 || B > h.max_B)
+    return fail(DKG_ERR_ARG, "dkg_debug_plan_qx32: output=%d outside [0, %d) or B=%d outside [1, %d]", output, h.m, B,
+                h.max_B);
+  const int rows = pad16(B), np = pad16(h.o[output].n), KB = np / 4;
+  std::vector<float> packed((size_t)rows * np);
+  hipStream_t s = (hipStream_t)stream;
+  int st;
+  if ((st = hip_check(hipMemcpyAsync(packed.data(), h.q32[output], packed.size() * sizeof(float),
+                                     hipMemcpyDeviceToHost, s), "hipMemcpyAsync(q32)")) ||
+      (st = hip_check(hipStreamSynchronize(s), "hipStreamSynchronize")))
+    return st;
+  // element (16 t + (l & 15), 4 kb + (l >> 4)) sits at frag32_index(t, kb, l, KB)
+  for (int r = 0; r < rows; ++r)
+    for (int c = 0; c < np; ++c)
+      host_out[(size_t)r * np + c] = packed[frag32_index(r >> 4, c >> 2, ((c & 3) << 4) | (r & 15), KB)];
+  return DKG_OK;
+}
+
+int dkg_debug_f32_dispatch(int max_n_pad, int d, int N, int m, int B, int geom_B, int out[6]) {
+  if (!out || max_n_pad < 16 || max_n_pad > 1024 || max_n_pad % 16 != 0 || d < 1 || d > DKG_MAX_DIM || N < 0 ||
+      m < 1 || m > DKG_MAX_OUTPUTS || B < 1 || geom_B < 0) {
+    fail(DKG_ERR_ARG, "dkg_debug_f32_dispatch: max_n_pad=%d d=%d N=%d m=%d B=%d geom_B=%d out=%s", max_n_pad, d, N, m,
+         B, geom_B, out ? "set" : "NULL");
+    return -2;
+  }
+  f32_dispatch(max_n_pad, d, N, m, B, geom_B, out);
   return 0;
 }
 

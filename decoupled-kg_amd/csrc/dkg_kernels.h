@@ -255,6 +255,12 @@ int set_cov_enabled(int mask);
 int set_cross_tall_mode(int mode);
 long long cross_tall_launches();
 bool cross_tall_eligible(int max_np, int d, int B, bool f32);
+// Which fp32 kernels a launch of B candidates (block shapes chosen for geom_B; 0: B) of an F32 plan takes, by
+// the launcher's own predicates (dkg_debug_f32_dispatch): out = {cross: 0 cross_root_plan_kernel<DM, float> /
+// 1 cross_big32_kernel, covariance: 0 posterior_cov_kernel<DM, float> / 1 posterior_cov_big32_kernel<DM>, DM,
+// the covariance launch's column blocks, row blocks, block order (-1: the narrow kernel has none)}.  The plan's
+// workspace is taken to hold the K(x, X) fill wherever a launch of B uses it (max_B >= B).  Host only.
+void f32_dispatch(int max_np, int d, int N, int m, int B, int geom_B, int out[6]);
 hipError_t launch_debug_mfma(const double* a, const double* b, double* c, hipStream_t s);
 
 // Launch geometry of the envelope stage for S scalarisation pairs: waves per workgroup and

@@ -650,6 +650,21 @@ static bool cross_big() {
   return !env || std::atoi(env) != 0;
 }
 
+// The dispatch of a launch's two contractions, stated once for the launcher (launch_cross_cov_tt) and the
+// dispatch query (f32_dispatch, dkg_debug_f32_dispatch): whether the cross stage fills K(x, X) with the separate
+// kernel (have_kx: the plan's workspace holds Plan::kx), whether it then takes the 64 x 32 blocks, and whether
+// an fp32 plan's covariance stage takes the 64 x 64 blocks (DKG_COV_BIG32=0: A/B only).  The fp32 blocks sum in
+// another order than the narrow fp32 kernels, so an F32 plan takes them only where one batch of the launch would
+// (geom_B): a launch of several batches keeps the per-batch bits (dkg_plan_forward_batches).
+static bool cross_fill_launch(bool have_kx, int max_np, int B) { return have_kx && cross_kfill_launch(max_np, B); }
+static bool cross_big_launch(bool use_kx, bool f32, int max_np, int geom_B) {
+  return use_kx && cross_big() && (!f32 || cross_kfill_launch(max_np, geom_B));
+}
+static bool cov_big32_launch(int dm, int N, int m, int geom_B) {
+  static const char* env = std::getenv("DKG_COV_BIG32");
+  return dm <= 8 && cov_big(N, geom_B, m) && (!env || std::atoi(env) != 0);
+}
+
 // cross_tall_kernel's dispatch (dkg_debug_cross_tall): -1 the default rule, 0 never, 1 every eligible shape
 // whatever the candidate count.  Atomics: the launcher threads read the mode while a test may set it.
 // DKG_CROSS_TALL=0 / 1 (A/B measurements) sets the initial mode.
@@ -693,6 +708,28 @@ static int cov_big_order(int nbx, int nby, int m) {
   return nbx >= 4 * nby ? 1 : 0;
 }
 
+// The 64 x 64 blocks' grid: column (line) blocks, row (candidate) blocks and their order.
+static void cov_big_grid(int N, int B, int m, int* nbx, int* nby, int* order) {
+  *nbx = (N + 16 * PB_CT - 1) / (16 * PB_CT);
+  *nby = (B + 16 * PB_RT - 1) / (16 * PB_RT);
+  *order = cov_big_order(*nbx, *nby, m);
+}
+
+void f32_dispatch(int max_np, int d, int N, int m, int B, int geom_B, int out[6]) {
+  const int gb = geom_B > 0 ? geom_B : B;  // (launch_stage)
+  const int dm = dim_bucket(d);
+  out[0] = cross_big_launch(cross_fill_launch(true, max_np, B), true, max_np, gb) ? 1 : 0;
+  out[1] = cov_big32_launch(dm, N, m, gb) ? 1 : 0;
+  out[2] = dm;
+  if (out[1]) {
+    cov_big_grid(N, B, m, &out[3], &out[4], &out[5]);
+  } else {  // posterior_cov_kernel's 32 x 32 blocks
+    out[3] = std::max(1, (N + 31) / 32);
+    out[4] = (B + 16 * PC_RB - 1) / (16 * PC_RB);
+    out[5] = -1;
+  }
+}
+
 template <int DM, class T>
 static hipError_t launch_cross_cov_tt(const Plan& h, const Plan* dev, const double* xnew, int B, double* kg,
                                       hipStream_t s, int stage, int geom_B) {
@@ -709,15 +746,13 @@ static hipError_t launch_cross_cov_tt(const Plan& h, const Plan* dev, const doub
         return hipGetLastError();
       }
     }
-    const int use_kx = (h.kx[0] != nullptr && cross_kfill_launch(h.max_np, B)) ? 1 : 0;
+    const int use_kx = cross_fill_launch(h.kx[0] != nullptr, h.max_np, B) ? 1 : 0;
     if (use_kx) {
       dim3 kgrid(pad16(B) / 16, (h.max_np / 4 + KF_KB - 1) / KF_KB, h.m);
       hipLaunchKernelGGL((cross_kfill_kernel<DM>), kgrid, dim3(KF_WAVES * WAVE), 0, s, dev, xnew, B);
     }
-    // K(x, X) in place: the 64 x 32 blocks, then the means and the clears.  The fp32 blocks sum in another order
-    // than cross_root_plan_kernel<float>, so an F32 plan takes them only where one batch of the launch would
-    // (geom_B): a launch of several batches keeps the per-batch bits (dkg_plan_forward_batches)
-    if (use_kx && cross_big() && (sizeof(T) == 8 || cross_kfill_launch(h.max_np, geom_B))) {
+    // K(x, X) in place: the 64 x 32 blocks, then the means and the clears (cross_big_launch: an F32 plan by geom_B)
+    if (cross_big_launch(use_kx != 0, sizeof(T) == 4, h.max_np, geom_B)) {
       const dim3 grid(cross_big_blocks(h.max_np, B, h.m) + pad16(B) / 16 * h.m);
       if constexpr (sizeof(T) == 8) {
         raise_lds_limit((const void*)cross_big_kernel, XB_LDS);
@@ -786,11 +821,10 @@ static hipError_t launch_cross_cov_tt(const Plan& h, const Plan* dev, const doub
       return hipGetLastError();
     }
   }
-  if constexpr (sizeof(T) == 4 && DM <= 8) {  // the fp32 plan's 64 x 64 blocks (DKG_COV_BIG32=0: A/B only)
-    static const char* env = std::getenv("DKG_COV_BIG32");
-    if (cov_big(h.N, geom_B, h.m) && (!env || std::atoi(env) != 0)) {  // (geom_B: as the cross stage above)
-      const int nbx = (h.N + 16 * PB_CT - 1) / (16 * PB_CT), nby = (B + 16 * PB_RT - 1) / (16 * PB_RT);
-      const int order = cov_big_order(nbx, nby, h.m);
+  if constexpr (sizeof(T) == 4 && DM <= 8) {  // the fp32 plan's 64 x 64 blocks
+    if (cov_big32_launch(DM, h.N, h.m, geom_B)) {  // (geom_B: as the cross stage above)
+      int nbx, nby, order;
+      cov_big_grid(h.N, B, h.m, &nbx, &nby, &order);
       dim3 grid(block_order_size(nbx, nby, h.m, order));
       raise_lds_limit((const void*)posterior_cov_big32_kernel<DM>, PB32_LDS);
       hipLaunchKernelGGL((posterior_cov_big32_kernel<DM>), grid, dim3(PB_WAVES * WAVE), PB32_LDS, s, dev, xnew, B,

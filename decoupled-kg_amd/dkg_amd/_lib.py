@@ -151,6 +151,8 @@ SIGNATURES = {
     "dkg_debug_cross_tall_launches": (ctypes.c_longlong, []),
     "dkg_debug_cross_tall_eligible": (c_int, [c_int, c_int, c_int, c_int]),
     "dkg_debug_plan_envelope": (c_int, [c_void_p, POINTER(c_int)]),
+    "dkg_debug_plan_qx32": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "dkg_debug_f32_dispatch": (c_int, [c_int] * 6 + [POINTER(c_int)]),
     "dkg_debug_mfma_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "dkg_debug_envelope_lds": (c_int, [c_int] * 9 + [POINTER(c_int)]),
 }

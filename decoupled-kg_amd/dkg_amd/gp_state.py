@@ -331,6 +331,23 @@ class DeviceGPState:
         return p.forward(X, kg_pairs=kg_pairs, timed=timed)
 
 
+F32_CROSS_KERNELS = ("cross_root_plan_kernel<DM, float>", "cross_big32_kernel")
+F32_COV_KERNELS = ("posterior_cov_kernel<DM, float>", "posterior_cov_big32_kernel<DM>")
+
+
+def f32_dispatch(max_n_pad: int, d: int, N: int, m: int, B: int, geom_B: int = 0) -> dict:
+    """Which fp32 kernels the cross and covariance stages of an fp32 plan launch for a shape, by the launcher's
+    own predicates (dkg_debug_f32_dispatch; host only): ``cross`` / ``cov`` are "narrow" or "big32" (``*_kernel``
+    the kernel's name), ``DM`` the dimension bucket, ``nbx`` / ``nby`` the covariance launch's line and candidate
+    blocks and ``order`` the 64 x 64 blocks' order (-1: the narrow kernel's 32 x 32 blocks have none)."""
+    out = (ctypes.c_int * 6)()
+    if _lib.load().dkg_debug_f32_dispatch(int(max_n_pad), int(d), int(N), int(m), int(B), int(geom_B), out) != 0:
+        _lib.check(_lib.DKG_ERR_ARG, "dkg_debug_f32_dispatch")
+    names = ("narrow", "big32")
+    return {"cross": names[out[0]], "cov": names[out[1]], "cross_kernel": F32_CROSS_KERNELS[out[0]],
+            "cov_kernel": F32_COV_KERNELS[out[1]], "DM": out[2], "nbx": out[3], "nby": out[4], "order": out[5]}
+
+
 # ForwardPlan(grad_rows=...): the plan flag of each mode
 GRAD_ROWS_FLAGS = {"staged": 0, "auto": _lib.DKG_PLAN_GRAD_GLOBAL_ROWS, "global": _lib.DKG_PLAN_FORCE_GLOBAL_ROWS}
 
@@ -438,6 +455,19 @@ class ForwardPlan:
         if _lib.load().dkg_debug_plan_envelope(self.host, out) != 0:
             _lib.check(_lib.DKG_ERR_ARG, "dkg_debug_plan_envelope")
         return {"slots": out[0], "stream": out[1], "sw": out[2], "split": out[3]}
+
+    def qx32(self, output: int, B: int) -> torch.Tensor:
+        """The fp32 ``Q_X = K(x, X) R`` of ``output`` as the last ``lines`` / forward of ``B`` candidates left it
+        (dkg_debug_plan_qx32; fp32 plans only): host float32 [pad16(B), n_pad], padding included."""
+        out = torch.empty(_pad16(B), _pad16(self.state.outputs[output].struct.n), dtype=torch.float32)
+        _lib.check(_lib.load().dkg_debug_plan_qx32(self.host, int(output), int(B), out.data_ptr(),
+                                                   current_stream_ptr(self.device)), "dkg_debug_plan_qx32")
+        return out
+
+    def f32_dispatch(self, B: int, geom_B: int = 0) -> dict:
+        """Which fp32 kernels a launch of ``B`` candidates of this plan's shape takes (``f32_dispatch``)."""
+        return f32_dispatch(max(_pad16(c.struct.n) for c in self.state.outputs), self.state.d, self.state.N,
+                            self.state.m, B, geom_B)
 
     def status(self, reset: bool = False) -> int:
         """The bits of the fused launches' in-launch waits that gave up since the last reset (0: every hand-off

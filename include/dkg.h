@@ -592,6 +592,26 @@ long long dkg_debug_cross_tall_launches(void);
  * -2 on bad arguments.  Host only: no device is touched. */
 int dkg_debug_cross_tall_eligible(int max_n_pad, int d, int B, int f32);
 
+/* The fp32 Q_X = K(x, X) R of output `output` (Plan::q32) as the last dkg_plan_lines or forward of B candidates
+ * on an initialised DKG_PLAN_F32 plan left it: copied to the host and unpacked from the quad-packed layout into
+ * host_out [n_pad16(B)][n_pad(output)] row-major (host memory; the padding rows and columns included).  No kernel
+ * is launched; `stream` (the plan's) is synchronised.  DKG_ERR_UNSUPPORTED for an fp64 plan, DKG_ERR_ARG for
+ * NULL pointers, an output outside [0, m) or B outside [1, max_B]. */
+int dkg_debug_plan_qx32(const void* host_plan, int output, int B, float* host_out, void* stream);
+
+/* Which fp32 kernels the cross and covariance stages of a DKG_PLAN_F32 plan launch for a shape, by the launcher's
+ * own predicates: widest padded n `max_n_pad` (a multiple of 16), input dimension d, N discretisation points, m
+ * outputs, B candidates in the launch, and geom_B the batch size the block shapes are chosen for (0: B; see
+ * dkg_plan_forward_batches).  The plan is taken to be sized for the launch (max_B >= B).
+ * out = {cross stage: 0 cross_root_plan_kernel<DM, float>, 1 cross_big32_kernel;
+ *        covariance stage: 0 posterior_cov_kernel<DM, float>, 1 posterior_cov_big32_kernel<DM>;
+ *        DM, the dimension bucket (2, 4, 8 or 16);
+ *        the covariance launch's column (line) blocks, row (candidate) blocks, and the 64 x 64 blocks' order
+ *        (-1 for the narrow kernel's 32 x 32 blocks)}.
+ * The environment variables DKG_CROSS_BIG / DKG_COV_BIG / DKG_COV_BIG32 / DKG_COV_ORDER count as in a launch.
+ * Returns 0, or -2 on bad arguments (dkg_last_error).  Host only: no device is touched. */
+int dkg_debug_f32_dispatch(int max_n_pad, int d, int N, int m, int B, int geom_B, int out[6]);
+
 /* Which kernels rank Q <= 2048 points when dkg_pareto_rank has a workspace (and every rank inside
  * dkg_pareto_nsga2).  mode -1: the measured rule (the default), 0: never the wide path, 1: always the wide path
  * (tests and A/B measurements).  Same bits either way; Q > 2048 is always the wide path.  Returns the previous

@@ -2,6 +2,9 @@
 for B candidates and one for 2B (the candidates twice).  Prints, per plan, the per-candidate relative slope
 error max_k |b32 - b64| / max_k |b64| (scalarisation 0) and the candidates whose error stands out.
 
+The asserted form of this view is tests/test_gpu_f32_model.py: the exported fp32 Q_X and the slopes against a
+per-stage rounding model (tests/f32_model.py) at ragged shapes, every fp32 kernel reached.
+
 usage: python tools/f32_debug.py [workload]   (DKG_COV_BIG32 / DKG_CROSS_BIG select the kernels)
 """
 import os
