@@ -26,6 +26,7 @@ from .gp_state import (
     state_stats,
 )
 from .jes import compute_sample_box_decomposition, qLowerBoundMultiObjectiveJointEntropySearch
+from .jes_pareto import sample_discrete_pareto_optimal_points, sample_rff_paths
 from .metrics import (
     calculate_reference_point,
     estimate_best_possible_expected_performance_after_scalarisation,
@@ -67,6 +68,8 @@ __all__ = [
     "nondominated_rank",
     "posterior_front_on_points",
     "sample_points_on_pareto_front",
+    "sample_discrete_pareto_optimal_points",
+    "sample_rff_paths",
     "calculate_reference_point",
     "estimate_best_possible_expected_performance_after_scalarisation",
     "estimate_expected_performance_after_scalarisation",

@@ -67,8 +67,29 @@ class DkgNsga2Params(ctypes.Structure):
         super().__init__(cr, eta_c, m, eta_m, int(raw_inputs), 0)
 
 
+DKG_RFF_MAX_FEATURES = 1024  # include/dkg.h: random Fourier features per path
+
+
+class DkgRffPaths(ctypes.Structure):
+    """``struct dkg_rff_paths`` (include/dkg.h): S sample paths of an m-output model."""
+
+    _fields_ = [("S", c_int32), ("m", c_int32), ("d", c_int32), ("R", c_int32), ("omega", c_void_p),
+                ("bias", c_void_p), ("coef", c_void_p), ("offset", c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/dkg.h declares.
 SIGNATURES = {
+    "dkg_rff_workspace": (c_size_t, [c_int, c_int]),
+    "dkg_rff_weights": (c_int, [POINTER(DkgOutput), c_int, c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_int, POINTER(DkgRffPaths), c_void_p, c_size_t, POINTER(c_double),
+                                c_void_p]),
+    "dkg_debug_rff_gram": (c_int, [c_int]),
+    "dkg_rff_eval": (c_int, [POINTER(DkgRffPaths), c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "dkg_pareto_paths_workspace": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dkg_pareto_nsga2_paths": (c_int, [POINTER(DkgRffPaths), c_void_p, c_void_p, c_int, c_int,
+                                       POINTER(DkgNsga2Params), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_size_t, c_void_p]),
+    "dkg_pareto_prune": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dkg_posterior_mean": (c_int, [POINTER(DkgOutput), c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "dkg_pareto_rank": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                 c_void_p]),

@@ -349,7 +349,8 @@ class JesOptimisationSpec:
 
     ``pareto_sampler(model, bounds, num_samples, target_num_points) -> (pareto_sets, pareto_fronts)`` is required:
     the reference samples GP paths by random Fourier features, runs NSGA-II on each and prunes the fronts
-    (``sample_discrete_pareto_optimal_points``, ``jes_sample_pareto.py``), which is not built here.  The sets are
+    (``sample_discrete_pareto_optimal_points``, ``jes_sample_pareto.py``); ``with_device_sampler`` builds a spec whose
+    sampler is this library's (``dkg_amd.jes_pareto``).  The sets are
     in the model's input space (the unit cube), the fronts in the untransformed output space; samples may hold
     different numbers of points.  The boxes come from ``compute_sample_box_decomposition`` (one or two
     objectives; ``hypercell_bounds_fn(pareto_fronts)`` replaces it for more).
@@ -375,6 +376,27 @@ class JesOptimisationSpec:
         # acquisition: None builds the device acquisition (tests inject the CPU restatement to compare runs)
         self.acq_factory = acq_factory
         self.hypercell_bounds_fn = hypercell_bounds_fn
+
+    @classmethod
+    def with_device_sampler(cls, estimation_type: str, num_pareto_samples: int, num_pareto_points: int,
+                            num_restarts: int, raw_samples: int, batch_limit: int, max_iter: int, device=None,
+                            seed: Optional[int] = None, acq_factory: Optional[Callable] = None,
+                            hypercell_bounds_fn: Optional[Callable] = None, **sampler_kwargs) -> "JesOptimisationSpec":
+        """A spec whose Pareto samples come from the device sampler
+        (``jes_pareto.sample_discrete_pareto_optimal_points``: random-Fourier-feature paths, NSGA-II and pruning,
+        ``jes_sample_pareto.py:48-98``), as the reference's spec does at
+        ``acquisition_optimisation_strategy.py:481-489, 526-534``.  ``sampler_kwargs`` go to the sampler
+        (``num_rffs``, ``nsga2_pop_size``, ``nsga2_generations``, ``mutation_prob``); ``seed`` seeds both the
+        sampler's draws and ``optimize_acqf``'s."""
+        from .jes_pareto import sample_discrete_pareto_optimal_points
+
+        def sampler(model, bounds, num_samples, target_num_points):
+            return sample_discrete_pareto_optimal_points(model, bounds, num_samples, target_num_points, seed=seed,
+                                                         device=device, **sampler_kwargs)
+
+        return cls(estimation_type, num_pareto_samples, num_pareto_points, num_restarts, raw_samples, batch_limit,
+                   max_iter, pareto_sampler=sampler, device=device, seed=seed, acq_factory=acq_factory,
+                   hypercell_bounds_fn=hypercell_bounds_fn)
 
     def _options(self) -> Dict:
         opts = {"batch_limit": self.batch_limit, "maxiter": self.max_iter}

@@ -40,6 +40,9 @@ extern "C" {
 #endif
 
 #define DKG_ABI_VERSION 9  /* 9: dkg_append_observation; 8: dkg_plan_forward_batches, dkg_plan_time_stage_batches */
+/* Added under 9 since (new symbols only; nothing that existed changed): dkg_mll_*, dkg_posterior_mean, dkg_pareto_*,
+ * dkg_jes_*, dkg_rff_workspace, dkg_rff_weights, dkg_rff_eval, dkg_debug_rff_gram, dkg_pareto_paths_workspace,
+ * dkg_pareto_nsga2_paths, dkg_pareto_prune. */
 #define DKG_MAX_OUTPUTS 8   /* outputs (objectives) per model list */
 #define DKG_MAX_DIM 16      /* input dimension d */
 
@@ -341,6 +344,109 @@ int dkg_jes_init(const dkg_output* states, int m, int P, int d, const double* bo
  * or B outside [1, max_B], checked before any HIP call. */
 int dkg_jes_forward(const void* host_plan, const double* x, int B, double* acq, double* dacq_dx, double* moments_out,
                     void* stream);
+
+/* ---- The Pareto samples of joint entropy search on the device (dkg_rff.hip) -----------------------------------
+ * The reference's sample_discrete_pareto_optimal_points (modules/pareto/jes_sample_pareto.py:48-232): per sample a
+ * posterior path of the model drawn with random Fourier features (BoTorch's get_gp_samples, :81-86), NSGA-II on the
+ * path (:146-207) and the pruning of its front by repeated crowding distance (:210-232).  Here every sample runs in
+ * the same launches.  fp64, stream ordered, every sum in a fixed order, no atomics on floating-point values, every
+ * random number from the caller.  All objectives are maximised.  DESIGN.md 8e states what differs from BoTorch and
+ * pymoo.  Limits (DKG_ERR_UNSUPPORTED beyond them): S <= DKG_JES_MAX_SAMPLES samples, R <= DKG_RFF_MAX_FEATURES
+ * features, m <= DKG_MAX_OUTPUTS, d <= DKG_MAX_DIM, n <= 1024; the arguments are checked before any HIP call. */
+#define DKG_RFF_MAX_FEATURES 1024
+/* S samples of an m-output model: sample s, output i is the function of the model inputs x
+ *   f(x) = offset[s][i] + sum_r coef[s][i][r] cos(omega[s][i][r] . x + bias[s][i][r]).
+ * Every pointer is a device allocation of the caller's. */
+typedef struct dkg_rff_paths {
+  int32_t S, m, d, R;
+  double* omega;  /* [S][m][R][d] */
+  double* bias;   /* [S][m][R] */
+  double* coef;   /* [S][m][R] */
+  double* offset; /* [S][m] */
+} dkg_rff_paths;
+
+/* Bytes of device scratch dkg_rff_weights needs for R features and outputs of at most n_max training points: eight
+ * problems' A, L^{-1} and Phi at a time.  0 outside 1 <= R <= DKG_RFF_MAX_FEATURES, 1 <= n_max <= 1024. */
+size_t dkg_rff_workspace(int R, int n_max);
+
+/* The weight-space posterior sample of every (sample, output): fills paths->omega, bias, coef, offset (paths->S,
+ * m, d, R give the sizes; m and d must equal the arguments).  Per (sample s, output i), from the caller's draws
+ * (device; standard normals wn [S][m][R][d] and z [S][m][R], g [S][m][R] draws of Gamma(shape nu, rate nu) for a
+ * Matern-nu output (not read for DKG_RBF; nullable when every output is DKG_RBF), uniforms ub [S][m][R] in [0, 1)):
+ *   omega_r = wn_r * inv_lengthscale * g_r^(-1/2)      (the factor g_r^(-1/2) = 1 / sqrt(g_r) for Matern only: the
+ *                                                       multivariate-t spectral density with 2 nu degrees of freedom)
+ *   b_r = 2 pi ub_r,  amp = sqrt(2 s / R),  Phi[k][r] = amp cos(omega_r . x_k + b_r)  over the output's n training
+ *                                                       rows; the phase is one fma per coordinate in order from 0,
+ *                                                       then + b_r
+ *   A = Phi^T Phi + noise I  (sums over the rows in order),  L = chol(A)
+ *   theta = L^{-T} (L^{-1} Phi^T (y - c) + sqrt(noise) z),  so theta ~ N(A^{-1} Phi^T (y - c), noise A^{-1})
+ *           (the products are with the explicit L^{-1}; the mean term A^{-1} Phi^T (y - c) is refined once against
+ *           L L^T, which brings it to the accuracy of a substitution solve)
+ *   coef_r = y_std amp theta_r,  offset = y_mean + y_std c
+ * outs: n, kernel, outputscale s, noise, mean_constant c, y_mean, y_std, inv_lengthscale and train_x are read;
+ * train_y: host array of m device pointers, [n] targets in model space.  The constant mean is taken off the targets
+ * and restored in the offset.  The factorisation is dkg_prepare_outputs' own (launch_cholesky_batch and
+ * launch_tri_inverse_batch over at most eight matrices per call, one status check per batch; a problem that fails is
+ * retried on its own with absolute jitter 1e-8 * 10^i, i < max_tries, added to the diagonal of A; theta keeps
+ * sqrt(noise)); DKG_ERR_NOT_PD if every attempt failed.  jitter_used: host [S][m], nullable.  work: device scratch
+ * of dkg_rff_workspace(R, max n) bytes (DKG_ERR_WORKSPACE when short).  Synchronises `stream` once per batch of
+ * eight problems (the retry policy reads the status).  A is conditioned like noise^-1 s n: at noise <= 1e-8 s the
+ * system is too ill-conditioned for any fp64 solve to pin theta; the sample is still a sample. */
+int dkg_rff_weights(const dkg_output* outs, int m, int d, const double* const* train_y, const double* wn,
+                    const double* g, const double* ub, const double* z, int max_tries, const dkg_rff_paths* paths,
+                    void* work, size_t work_bytes, double* jitter_used, void* stream);
+
+/* Which kernel forms Phi^T Phi: 0 tiles of v_mfma_f64_16x16x4_f64 (the default), 1 VALU fma tiles (A/B
+ * measurements; the two round differently), -1 only reads.  Returns the previous mode, -2 on a bad one. */
+int dkg_debug_rff_gram(int mode);
+
+/* Dynamic LDS of the path evaluation's workgroup: one output's omega [R][d], bias [R] and coef [R].  At the limits
+ * (R = 1024, d = 16) it is 144 KiB of the 160 KiB a workgroup can have, so nothing is staged in halves. */
+#define DKG_RFF_EVAL_LDS_BYTES(R, d) ((size_t)(R) * ((d) + 2) * 8)
+
+/* F[s][p][i] = f_{s,i}(x_{s,p}) for x device [S][P][d] (shared_x = 0) or one [P][d] evaluated by every sample
+ * (shared_x != 0); F device [S][P][m].  One workgroup per (sample, output, 16 points) stages the output's (omega,
+ * bias, coef) in LDS once; one wave per point; lane l owns the features l, l + 64, ...: the phase is one fma per
+ * coordinate in order from 0, then + bias_r, and acc = fma(cos(phase), coef_r, acc) is one chain per lane; wave_sum's fixed-order
+ * reduction; F = offset + sum.  A point's bits depend on the point and its path alone: not on P, on its row, or on
+ * the samples evaluated beside it (a struct whose pointers start at sample s evaluates that sample alone).
+ * P = 0 is a no-op. */
+int dkg_rff_eval(const dkg_rff_paths* paths, const double* x, int P, int shared_x, double* F, void* stream);
+
+/* Bytes of device scratch dkg_pareto_nsga2_paths needs (0 outside the limits). */
+size_t dkg_pareto_paths_workspace(int S, int P, int d, int m);
+
+/* dkg_pareto_nsga2 for S populations at once, population s evolving on sample s of `paths`: every launch carries a
+ * sample axis (init; then per generation the variation, which also copies the parents; dkg_rff_eval of the children;
+ * the one-workgroup rank of the 2P points, one workgroup per sample; the gather).  Four launches per generation
+ * whatever S is, no host synchronisation.
+ *   uniforms: device [S][P d + gens * dkg_pareto_draws(P, d)], sample s's row laid out as dkg_pareto_nsga2's
+ *   lb, ub  : device [d], shared by the samples; the path takes (x - lb) / (ub - lb) unless prm->raw_inputs
+ *   X [S][P][d], F [S][P][m], rank [S][P], crowd [S][P]: device, the final populations and their rankings
+ *   work    : device scratch of dkg_pareto_paths_workspace(S, P, d, m) bytes
+ * Sample s of the result has exactly the bits the stage entries give for that sample alone (dkg_pareto_variation,
+ * dkg_rff_eval on sample s, dkg_pareto_rank with keep = P, the survivors in `order` order), and so the bits of an
+ * S = 1 call on sample s with its row of uniforms.  P as dkg_pareto_nsga2 (a multiple of 4, 8 <= P <= 1024). */
+int dkg_pareto_nsga2_paths(const dkg_rff_paths* paths, const double* lb, const double* ub, int P, int gens,
+                           const dkg_nsga2_params* prm, const double* uniforms, double* X, double* F, int* rank,
+                           double* crowd, void* work, size_t work_bytes, void* stream);
+
+/* The reference's prune_pareto_front (jes_sample_pareto.py:210-232) on the non-dominated members of S populations
+ * F (device [S][Q][m]) ranked by `rank` (device [S][Q], as dkg_pareto_rank leaves it), one workgroup per sample:
+ *   - the members are the points of rank 0 (pymoo's result is the non-dominated set, :207);
+ *   - of members with bit-equal objective vectors only the lowest index stays (eliminate_duplicates, :202);
+ *   - while more than k members are left: the crowding distance of each within the set that is left, by
+ *     dkg_pareto_rank's arithmetic (per objective in order one subtraction, division and addition, no fused
+ *     multiply-add; the ends +inf), and the member of smallest (crowding, index) is retired.  The reference breaks
+ *     ties at random; here the lowest index goes.
+ *   count [S]: the members left (<= k);  index [S][k]: their indices ascending, then -1.
+ * 1 <= Q <= 2048, 1 <= k <= 2048, S <= DKG_JES_MAX_SAMPLES, m <= DKG_MAX_OUTPUTS.
+ * Cost: every retirement is a round of the sample's one workgroup in which each member left rescans the Q points
+ * per objective, so a sample takes (members - k) rounds of O(Q m) each, one after the other: 90 rounds at the
+ * preset (100 members to 10), but about 2047 rounds of 4096 m reads per thread at Q = 2048, all of rank 0, k = 1
+ * (tens of milliseconds).  Sized for populations, not for the 16384-point fronts of dkg_pareto_rank. */
+int dkg_pareto_prune(const double* F, const int* rank, int S, int Q, int m, int k, int* count, int* index,
+                     void* stream);
 
 /* Bytes of scratch dkg_forward needs for (m outputs, N points, B candidates, S weights). */
 size_t dkg_forward_workspace(const dkg_output* outs, int m, int N, int B, int S);
