@@ -35,6 +35,21 @@ int dkg::report_error(int code, const char* msg) {
   return code;
 }
 
+int dkg::failf(int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  return report_error(code, buf);
+}
+
+int dkg::hip_status(hipError_t e, const char* what) {
+  return e == hipSuccess ? DKG_OK : failf(DKG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+}
+
+size_t dkg::up256(size_t x) { return (x + 255) & ~(size_t)255; }
+
 namespace {
 
 int hip_check(hipError_t e, const char* what) {

@@ -438,6 +438,15 @@ __device__ __forceinline__ double wave_max(double v) {
   return combine_rows(v, [](double a, double b) { return fmax(a, b); });
 }
 
+__device__ __forceinline__ double clip(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// (x - lo) / (hi - lo), each operation rounded on its own: botorch's normalize (sample.py:129-130, 142), the bits a
+// host computes.  The evaluators of the NSGA-II (posterior_mean_kernel, rff_eval_kernel) map a point with it.
+__device__ __forceinline__ double unit_cube(double x, double lo, double hi) {
+#pragma clang fp contract(off)
+  return (x - lo) / (hi - lo);
+}
+
 // Wave ballot of a compare: the compare's lane mask itself (HIP's __ballot
 // goes through an int and costs a v_cndmask + v_cmp per use).
 __device__ __forceinline__ uint64_t ballot(bool c) { return __builtin_amdgcn_ballot_w64(c); }

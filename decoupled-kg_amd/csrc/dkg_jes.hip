@@ -24,8 +24,6 @@
 //                        chain rule to dx ends here with the moments stage's dmu/dx and dvar/dx.  The states
 //                        meet in LDS and are summed in index order.  No atomics anywhere: two calls give the
 //                        same bits, and a candidate's result does not depend on B or on its row.
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 
 #include "dkg_stages.h"
@@ -549,21 +547,6 @@ using namespace dkg;
 
 namespace {
 
-int jfail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return report_error(code, buf);
-}
-
-int jhip(hipError_t e, const char* what) {
-  return e == hipSuccess ? DKG_OK : jfail(DKG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // the workspace carve: the state table, then the moments and their x-gradients
 struct JesWs {
   size_t tab, mu, q2, dmu, dvar, total;
@@ -589,14 +572,14 @@ JesWs jes_ws(int m, int P, int d, int max_B) {
 // sizes only (dkg_jes_workspace and dkg_jes_init share it); 0 when they are fine
 int check_sizes(int m, int P, int d, int J, int max_B) {
   if (m < 1 || P < 1 || d < 1 || J < 1 || max_B < 1)
-    return jfail(DKG_ERR_ARG, "m=%d P=%d d=%d J=%d max_B=%d", m, P, d, J, max_B);
-  if (m > DKG_MAX_OUTPUTS) return jfail(DKG_ERR_UNSUPPORTED, "m=%d outputs (supported <= %d)", m, DKG_MAX_OUTPUTS);
-  if (d > DKG_MAX_DIM) return jfail(DKG_ERR_UNSUPPORTED, "d=%d (supported 1..%d)", d, DKG_MAX_DIM);
+    return failf(DKG_ERR_ARG, "m=%d P=%d d=%d J=%d max_B=%d", m, P, d, J, max_B);
+  if (m > DKG_MAX_OUTPUTS) return failf(DKG_ERR_UNSUPPORTED, "m=%d outputs (supported <= %d)", m, DKG_MAX_OUTPUTS);
+  if (d > DKG_MAX_DIM) return failf(DKG_ERR_UNSUPPORTED, "d=%d (supported 1..%d)", d, DKG_MAX_DIM);
   if (P > DKG_JES_MAX_SAMPLES)
-    return jfail(DKG_ERR_UNSUPPORTED, "P=%d Pareto samples (supported <= %d)", P, DKG_JES_MAX_SAMPLES);
-  if (J > DKG_JES_MAX_BOXES) return jfail(DKG_ERR_UNSUPPORTED, "J=%d boxes (supported <= %d)", J, DKG_JES_MAX_BOXES);
+    return failf(DKG_ERR_UNSUPPORTED, "P=%d Pareto samples (supported <= %d)", P, DKG_JES_MAX_SAMPLES);
+  if (J > DKG_JES_MAX_BOXES) return failf(DKG_ERR_UNSUPPORTED, "J=%d boxes (supported <= %d)", J, DKG_JES_MAX_BOXES);
   if (max_B > DKG_JES_MAX_CANDIDATES)
-    return jfail(DKG_ERR_UNSUPPORTED, "max_B=%d candidates (supported <= %d)", max_B, DKG_JES_MAX_CANDIDATES);
+    return failf(DKG_ERR_UNSUPPORTED, "max_B=%d candidates (supported <= %d)", max_B, DKG_JES_MAX_CANDIDATES);
   return DKG_OK;
 }
 
@@ -619,26 +602,26 @@ size_t dkg_jes_workspace(int m, int P, int d, int J, int max_B) {
 
 int dkg_jes_init(const dkg_output* states, int m, int P, int d, const double* bounds, int J, int target,
                  int only_diagonal, int max_B, void* workspace, size_t workspace_bytes, void* host_plan, void* stream) {
-  if (!states || !bounds || !workspace || !host_plan) return jfail(DKG_ERR_ARG, "NULL pointer");
+  if (!states || !bounds || !workspace || !host_plan) return failf(DKG_ERR_ARG, "NULL pointer");
   int st = check_sizes(m, P, d, J, max_B);
   if (st) return st;
-  if (target < -1 || target >= m) return jfail(DKG_ERR_ARG, "target=%d outside [-1, %d)", target, m);
+  if (target < -1 || target >= m) return failf(DKG_ERR_ARG, "target=%d outside [-1, %d)", target, m);
   const int SO = (P + 1) * m;
   int max_np = 16;
   for (int k = 0; k < SO; ++k) {
     const dkg_output& o = states[k];
-    if (o.n < 1) return jfail(DKG_ERR_ARG, "state %d output %d: n=%d training points", k / m, k % m, o.n);
+    if (o.n < 1) return failf(DKG_ERR_ARG, "state %d output %d: n=%d training points", k / m, k % m, o.n);
     if (o.n > 1024)
-      return jfail(DKG_ERR_UNSUPPORTED, "state %d output %d: n=%d > 1024 training points", k / m, k % m, o.n);
+      return failf(DKG_ERR_UNSUPPORTED, "state %d output %d: n=%d > 1024 training points", k / m, k % m, o.n);
     if (o.kernel < DKG_MATERN12 || o.kernel > DKG_RBF)
-      return jfail(DKG_ERR_ARG, "state %d output %d: kernel id %d", k / m, k % m, o.kernel);
+      return failf(DKG_ERR_ARG, "state %d output %d: kernel id %d", k / m, k % m, o.kernel);
     if (!o.inv_lengthscale || !o.train_x || !o.alpha || !o.root_frag)
-      return jfail(DKG_ERR_ARG, "state %d output %d: NULL pointer", k / m, k % m);
+      return failf(DKG_ERR_ARG, "state %d output %d: NULL pointer", k / m, k % m);
     max_np = std::max(max_np, pad16(o.n));
   }
   const JesWs w = jes_ws(m, P, d, max_B);
   if (workspace_bytes < w.total)
-    return jfail(DKG_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, w.total);
+    return failf(DKG_ERR_WORKSPACE, "workspace %zu bytes < required %zu", workspace_bytes, w.total);
   JesHost* h = static_cast<JesHost*>(host_plan);
   std::memset(h, 0, sizeof(JesHost));
   std::memcpy(h->tab, states, (size_t)SO * sizeof(dkg_output));
@@ -652,7 +635,7 @@ int dkg_jes_init(const dkg_output* states, int m, int P, int d, const double* bo
   p.q2 = reinterpret_cast<double*>(base + w.q2);
   p.dmu = reinterpret_cast<double*>(base + w.dmu);
   p.dvar = reinterpret_cast<double*>(base + w.dvar);
-  st = jhip(hipMemcpyAsync(base + w.tab, h->tab, (size_t)SO * sizeof(dkg_output), hipMemcpyHostToDevice,
+  st = hip_status(hipMemcpyAsync(base + w.tab, h->tab, (size_t)SO * sizeof(dkg_output), hipMemcpyHostToDevice,
                            (hipStream_t)stream), "dkg_jes_init: table upload");
   if (st) return st;
   p.magic = JES_MAGIC;
@@ -661,10 +644,10 @@ int dkg_jes_init(const dkg_output* states, int m, int P, int d, const double* bo
 
 int dkg_jes_forward(const void* host_plan, const double* x, int B, double* acq, double* dacq_dx, double* moments_out,
                     void* stream) {
-  if (!host_plan || !x || !acq) return jfail(DKG_ERR_ARG, "NULL pointer");
+  if (!host_plan || !x || !acq) return failf(DKG_ERR_ARG, "NULL pointer");
   const JesPlan& p = static_cast<const JesHost*>(host_plan)->plan;
-  if (p.magic != JES_MAGIC) return jfail(DKG_ERR_ARG, "the plan is not initialised (dkg_jes_init)");
-  if (B < 1 || B > p.max_B) return jfail(DKG_ERR_ARG, "B=%d candidates outside [1, max_B=%d]", B, p.max_B);
+  if (p.magic != JES_MAGIC) return failf(DKG_ERR_ARG, "the plan is not initialised (dkg_jes_init)");
+  if (B < 1 || B > p.max_B) return failf(DKG_ERR_ARG, "B=%d candidates outside [1, max_B=%d]", B, p.max_B);
   hipStream_t s = (hipStream_t)stream;
   const int grad = dacq_dx != nullptr;
   JesMomArgs ma{p.tab, x, p.mu, p.q2, p.dmu, p.dvar, B, p.d, p.bpad, grad};
@@ -676,7 +659,7 @@ int dkg_jes_forward(const void* host_plan, const double* x, int B, double* acq, 
     case 8: launch_lds(jes_moments_kernel<8>, mgrid, mblock, mlds, s, ma); break;
     default: launch_lds(jes_moments_kernel<16>, mgrid, mblock, mlds, s, ma); break;
   }
-  int st = jhip(hipGetLastError(), "jes_moments_kernel");
+  int st = hip_status(hipGetLastError(), "jes_moments_kernel");
   if (st) return st;
   JesEntArgs ea{p.tab, p.bounds, p.mu, p.q2, p.dmu, p.dvar, acq, dacq_dx, moments_out,
                 p.m, p.P, p.d, p.J, p.target, p.only_diag, B, p.bpad, grad};
@@ -686,7 +669,7 @@ int dkg_jes_forward(const void* host_plan, const double* x, int B, double* acq, 
   else if (p.m == 2) hipLaunchKernelGGL(jes_entropy_kernel<2>, egrid, eblock, elds, s, ea);
   else if (p.m <= 4) hipLaunchKernelGGL(jes_entropy_kernel<4>, egrid, eblock, elds, s, ea);
   else hipLaunchKernelGGL(jes_entropy_kernel<8>, egrid, eblock, elds, s, ea);
-  return jhip(hipGetLastError(), "jes_entropy_kernel");
+  return hip_status(hipGetLastError(), "jes_entropy_kernel");
 }
 
 }  // extern "C"

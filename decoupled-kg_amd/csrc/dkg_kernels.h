@@ -233,6 +233,17 @@ hipError_t launch_forward(const Plan& host, const Plan* dev, const double* xnew,
 size_t fused_lds_bytes_host(const Plan& h);
 // Sets dkg_last_error()'s thread-local message (host translation units other than dkg_abi.hip); returns code.
 int report_error(int code, const char* msg);
+// The same with a printf-style message; a hipError_t as a status (DKG_OK, or DKG_ERR_HIP and "what: the runtime's
+// text"); the 256-byte rounding of the workspace carves.  Defined once, in dkg_abi.hip.
+int failf(int code, const char* fmt, ...);
+int hip_status(hipError_t e, const char* what);
+size_t up256(size_t x);
+// dkg_rff.hip.  The argument check of a dkg_rff_paths, and the values of its S paths: sample s's points [P][d] at
+// x + s * x_stride (0: every sample evaluates the same points) into F + s * f_stride [P][m]; lb / ub not NULL: the
+// model input is unit_cube(x, lb, ub).
+int check_rff_paths(const dkg_rff_paths* p);
+hipError_t launch_rff_eval(const dkg_rff_paths& p, const double* x, size_t x_stride, double* F, size_t f_stride,
+                           const double* lb, const double* ub, int P, hipStream_t s);
 hipError_t launch_forward_auto(const Plan& host, const Plan* dev, const double* xnew, int B, double* kg,
                                double* pairs, hipStream_t s);
 // Envelope stage alone over P sets of L lines: KG, envelope sizes (nullable) and, when idx is given, the

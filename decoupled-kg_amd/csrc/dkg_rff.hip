@@ -1,7 +1,7 @@
-// Pareto samples for joint entropy search on the device (gfx950): random-Fourier-feature posterior paths, their
-// evaluation, NSGA-II on every path side by side, and the pruning of the fronts.  The reference draws the paths with
-// BoTorch's get_gp_samples and runs pymoo's NSGA-II on each, one after the other, then prunes by repeated crowding
-// distance (modules/pareto/jes_sample_pareto.py:48-232).  Specification: include/dkg.h; DESIGN.md 8e.
+// Sample paths for joint entropy search on the device (gfx950): random-Fourier-feature posterior paths and their
+// evaluation.  The reference draws the paths with BoTorch's get_gp_samples (modules/pareto/jes_sample_pareto.py:81-86);
+// the NSGA-II that runs on them and the pruning of its fronts are dkg_pareto.hip's, which takes launch_rff_eval as its
+// fitness.  Specification: include/dkg.h; DESIGN.md 8e.
 //
 //   rff_feature_kernel   omega, bias and Phi [n][R] of up to 8 (sample, output) problems: lane = feature, wave = row
 //   rff_gram_kernel      A = Phi^T Phi + diag I in 32 x 32 tiles of v_mfma_f64_16x16x4_f64, k in order
@@ -9,18 +9,14 @@
 //   launch_cholesky_batch / launch_tri_inverse_batch (dkg_linalg.hip): L = chol(A), X = L^{-1}
 //   rff_theta_kernel     theta = X^T (X Phi^T r + sqrt(noise) z), coef and offset; one workgroup per problem
 //   rff_eval_kernel      F[s][p][i]: one workgroup per (sample, output, 16 points), (omega, bias, coef) in LDS, one
-//                        wave per point, lane l the features l, l + 64, ... as one fma chain, then wave_sum
-//   paths_*_kernel       dkg_pareto_nsga2's generation with a sample axis in every grid; the rank and the variation
-//                        are dkg_pareto.hip's own bodies (dkg_pareto_dev.h)
-//   pareto_prune_kernel  one workgroup per sample: duplicates, then the member of smallest (crowding, index) retired
-//                        until k are left, the crowding by the rank's own arithmetic (front_crowding)
+//                        wave per point, lane l the features l, l + 64, ... as one fma chain, then wave_sum; the
+//                        points as given or mapped to the unit cube with lb / ub (launch_rff_eval, dkg_kernels.h)
 // fp64 throughout; every sum runs in a fixed order; no atomics on floating-point values.
+#include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 
-#include "dkg_pareto_dev.h"
+#include "dkg_kernels.h"
 
 namespace dkg {
 
@@ -215,11 +211,6 @@ struct EvalArgs {
   int P;
 };
 
-__device__ __forceinline__ double unit_cube(double x, double lo, double hi) {
-#pragma clang fp contract(off)
-  return (x - lo) / (hi - lo);
-}
-
 // Grid (P / 16, m, S).  LDS (DKG_RFF_EVAL_LDS_BYTES): omega transposed [d][R] (a lane's reads are then a stride of
 // one double), bias [R], coef [R].  A point's value is its own lane chains and wave_sum: the same bits whatever P,
 // its row, and the samples beside it.
@@ -270,7 +261,9 @@ __global__ __launch_bounds__(RE_WAVES* WAVE) void rff_eval_kernel(EvalArgs a) {
   }
 }
 
-static hipError_t launch_eval(const EvalArgs& a, hipStream_t s) {
+hipError_t launch_rff_eval(const dkg_rff_paths& p, const double* x, size_t x_stride, double* F, size_t f_stride,
+                           const double* lb, const double* ub, int P, hipStream_t s) {
+  const EvalArgs a{p, x, x_stride, F, f_stride, lb, ub, P};
   const size_t lds = DKG_RFF_EVAL_LDS_BYTES(a.p.R, a.p.d);
   const dim3 grid((a.P + RE_POINTS - 1) / RE_POINTS, a.p.m, a.p.S), block(RE_WAVES * WAVE);
   auto go = [&](auto kern) {
@@ -286,187 +279,17 @@ static hipError_t launch_eval(const EvalArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// dkg_pareto_nsga2's generation, blockIdx.y the sample.
-struct PathsGen {
-  const double *lb, *ub;
-  const double* u;     // sample s's uniforms at u + s * u_stride
-  size_t u_stride;
-  size_t u_off;        // this generation's draws within a sample's uniforms
-  double *X, *F, *crowd;     // [S][P][d], [S][P][m], [S][P]
-  int* rank;                 // [S][P]
-  double *X2, *F2, *crowd2;  // [S][2P][d], [S][2P][m], [S][2P]
-  int *rank2, *order;        // [S][2P]
-  int P, d, m;
-  double cr, eta_c, pm, eta_m;
-};
-
-// x[s][p][k] = lb[k] + u[s][p][k] (ub[k] - lb[k]), clipped into the bounds (pareto_init_kernel's arithmetic)
-__global__ __launch_bounds__(256) void paths_init_kernel(PathsGen g) {
-#pragma clang fp contract(off)
-  const int t = blockIdx.x * blockDim.x + threadIdx.x, s = blockIdx.y;
-  const int total = g.P * g.d;
-  if (t >= total) return;
-  const int k = t % g.d;
-  g.X[(size_t)s * total + t] = clip(g.lb[k] + g.u[s * g.u_stride + t] * (g.ub[k] - g.lb[k]), g.lb[k], g.ub[k]);
-}
-
-// The parents into the first half of [parents; children], and the children by pareto_variation_body
-__global__ __launch_bounds__(256) void paths_variation_kernel(PathsGen g) {
-  const int s = blockIdx.y, P = g.P, d = g.d, m = g.m;
-  const int t = blockIdx.x * blockDim.x + threadIdx.x, nt = gridDim.x * blockDim.x;
-  const double* X = g.X + (size_t)s * P * d;
-  const double* F = g.F + (size_t)s * P * m;
-  double* X2 = g.X2 + (size_t)s * 2 * P * d;
-  double* F2 = g.F2 + (size_t)s * 2 * P * m;
-  for (int e = t; e < P * d; e += nt) X2[e] = X[e];
-  for (int e = t; e < P * m; e += nt) F2[e] = F[e];
-  VarArgs a{X, g.rank + (size_t)s * P, g.crowd + (size_t)s * P, g.lb, g.ub, g.u + s * g.u_stride + g.u_off,
-            X2 + (size_t)P * d, P, d, g.cr, g.eta_c, g.pm, g.eta_m};
-  pareto_variation_body(a, t);
-}
-
-// One workgroup per sample ranks its Q points (pareto_rank_body); out arrays [S][Q]
-template <int MB>
-__global__ __launch_bounds__(1024) void paths_rank_kernel(const double* __restrict__ F, int Q, int m, int keep,
-                                                          int* __restrict__ rank, double* __restrict__ crowd,
-                                                          int* __restrict__ order) {
-  extern __shared__ __attribute__((aligned(16))) double pr_smem[];
-  const size_t s = blockIdx.x;
-  pareto_rank_body<MB>(F + s * Q * m, Q, m, keep, rank + s * Q, crowd + s * Q, order + s * Q, pr_smem);
-}
-
-static hipError_t launch_paths_rank(const double* F, int S, int Q, int m, int keep, int* rank, double* crowd,
-                                    int* order, hipStream_t st) {
-  const size_t lds = rank_lds_bytes(Q, m);
-  const int nt = rank_threads(Q);
-  auto go = [&](auto kern) {
-    raise_lds_limit(reinterpret_cast<const void*>(kern), lds);
-    hipLaunchKernelGGL(kern, dim3(S), dim3(nt), lds, st, F, Q, m, keep, rank, crowd, order);
-  };
-  if (m <= 2) go(paths_rank_kernel<2>);
-  else if (m <= 4) go(paths_rank_kernel<4>);
-  else go(paths_rank_kernel<8>);
-  return hipGetLastError();
-}
-
-// survivor r of sample s = point order[s][r] of its [parents; children]
-__global__ __launch_bounds__(256) void paths_gather_kernel(PathsGen g) {
-  const int s = blockIdx.y, P = g.P, d = g.d, m = g.m;
-  const int w = d + m + 2;
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= P * w) return;
-  const int r = t / w, c = t - r * w;
-  const int src = g.order[(size_t)s * 2 * P + r];
-  if (src < 0 || src >= 2 * P) return;  // never for r < keep; keeps a bad order in bounds
-  const size_t s2 = (size_t)s * 2 * P + src, s1 = (size_t)s * P + r;
-  if (c < d) g.X[s1 * d + c] = g.X2[s2 * d + c];
-  else if (c < d + m) g.F[s1 * m + (c - d)] = g.F2[s2 * m + (c - d)];
-  else if (c == d + m) g.rank[s1] = g.rank2[s2];
-  else g.crowd[s1] = g.crowd2[s2];
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Pruning.  One workgroup per sample; LDS: F [Q][m], alive [Q] (0 alive, -1 not: front_crowding's front 0).
-__host__ __device__ inline size_t prune_lds_bytes(int Q, int m) {
-  return (size_t)Q * m * sizeof(double) + (size_t)Q * sizeof(int);
-}
-
-__global__ __launch_bounds__(1024) void pareto_prune_kernel(const double* __restrict__ F, const int* __restrict__ rank,
-                                                            int Q, int m, int k, int* __restrict__ count,
-                                                            int* __restrict__ index) {
-  extern __shared__ __attribute__((aligned(16))) double pp_smem[];
-  __shared__ double red_cd[16];
-  __shared__ int red_ix[16];
-  double* f = pp_smem;
-  int* alive = reinterpret_cast<int*>(pp_smem + (size_t)Q * m);
-  const size_t s = blockIdx.x;
-  F += s * Q * m;
-  rank += s * Q;
-  index += s * k;
-  const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
-  for (int e = tid; e < Q * m; e += nt) f[e] = F[e];
-  for (int e = tid; e < Q; e += nt) alive[e] = rank[e] == 0 ? 0 : -1;
-  for (int e = tid; e < k; e += nt) index[e] = -1;
-  __syncthreads();
-  // of members with bit-equal objective vectors the lowest index stays
-  bool dup[PR_PPT];
-#pragma unroll
-  for (int sl = 0; sl < PR_PPT; ++sl) {
-    const int i = tid + sl * nt;
-    dup[sl] = false;
-    if (i >= Q || alive[i] != 0) continue;
-    for (int j = 0; j < i && !dup[sl]; ++j) {
-      if (alive[j] != 0) continue;
-      bool same = true;
-      for (int c = 0; c < m; ++c)
-        same = same && __double_as_longlong(f[(size_t)i * m + c]) == __double_as_longlong(f[(size_t)j * m + c]);
-      dup[sl] = same;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int sl = 0; sl < PR_PPT; ++sl)
-    if (dup[sl]) alive[tid + sl * nt] = -1;
-  __syncthreads();
-  int cnt = 0;
-#pragma unroll
-  for (int sl = 0; sl < PR_PPT; ++sl) {
-    const int i = tid + sl * nt;
-    cnt += __syncthreads_count(i < Q && alive[i] == 0);
-  }
-  while (cnt > k) {  // uniform
-    double bcd = __builtin_inf();
-    int bix = 0x7fffffff;
-#pragma unroll
-    for (int sl = 0; sl < PR_PPT; ++sl) {
-      const int i = tid + sl * nt;
-      if (i >= Q || alive[i] != 0) continue;
-      const double cd = front_crowding(f, alive, Q, m, i, 0);
-      if (cd < bcd || (cd == bcd && i < bix)) {
-        bcd = cd;
-        bix = i;
-      }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const double ocd = __shfl_xor(bcd, off);
-      const int oix = __shfl_xor(bix, off);
-      if (ocd < bcd || (ocd == bcd && oix < bix)) {
-        bcd = ocd;
-        bix = oix;
-      }
-    }
-    if (lane == 0) {
-      red_cd[wave] = bcd;
-      red_ix[wave] = bix;
-    }
-    __syncthreads();
-    bcd = red_cd[0];
-    bix = red_ix[0];
-    for (int w2 = 1; w2 < nw; ++w2) {
-      const double ocd = red_cd[w2];
-      const int oix = red_ix[w2];
-      if (ocd < bcd || (ocd == bcd && oix < bix)) {
-        bcd = ocd;
-        bix = oix;
-      }
-    }
-    __syncthreads();  // every thread has read the wave results and this round's alive set
-    if (bix >= Q) break;  // never: cnt > k >= 1 members are alive
-    if (tid == 0) alive[bix] = -1;
-    __syncthreads();
-    --cnt;
-  }
-  if (tid == 0) count[s] = cnt;
-#pragma unroll
-  for (int sl = 0; sl < PR_PPT; ++sl) {
-    const int i = tid + sl * nt;
-    if (i >= Q || alive[i] != 0) continue;
-    int pos = 0;
-    for (int j = 0; j < i; ++j) pos += alive[j] == 0 ? 1 : 0;
-    if (pos < k) index[pos] = i;
-  }
+int check_rff_paths(const dkg_rff_paths* p) {
+  if (!p) return failf(DKG_ERR_ARG, "NULL pointer");
+  if (p->S < 1 || p->m < 1 || p->d < 1 || p->R < 1)
+    return failf(DKG_ERR_ARG, "paths S=%d m=%d d=%d R=%d", p->S, p->m, p->d, p->R);
+  if (p->S > DKG_JES_MAX_SAMPLES)
+    return failf(DKG_ERR_UNSUPPORTED, "S=%d samples (supported <= %d)", p->S, DKG_JES_MAX_SAMPLES);
+  if (p->m > DKG_MAX_OUTPUTS) return failf(DKG_ERR_UNSUPPORTED, "m=%d outputs (supported <= %d)", p->m, DKG_MAX_OUTPUTS);
+  if (p->d > DKG_MAX_DIM) return failf(DKG_ERR_UNSUPPORTED, "d=%d (supported 1..%d)", p->d, DKG_MAX_DIM);
+  if (p->R > RFF_MAXR) return failf(DKG_ERR_UNSUPPORTED, "R=%d features (supported <= %d)", p->R, RFF_MAXR);
+  if (!p->omega || !p->bias || !p->coef || !p->offset) return failf(DKG_ERR_ARG, "paths: NULL pointer");
+  return DKG_OK;
 }
 
 }  // namespace dkg
@@ -475,41 +298,7 @@ using namespace dkg;
 
 namespace {
 
-int rfail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return report_error(code, buf);
-}
-
-int rhip(hipError_t e, const char* what) {
-  return e == hipSuccess ? DKG_OK : rfail(DKG_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
-
-size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 std::atomic<int> g_rff_gram_valu{0};
-
-int check_paths(const dkg_rff_paths* p) {
-  if (!p) return rfail(DKG_ERR_ARG, "NULL pointer");
-  if (p->S < 1 || p->m < 1 || p->d < 1 || p->R < 1)
-    return rfail(DKG_ERR_ARG, "paths S=%d m=%d d=%d R=%d", p->S, p->m, p->d, p->R);
-  if (p->S > DKG_JES_MAX_SAMPLES)
-    return rfail(DKG_ERR_UNSUPPORTED, "S=%d samples (supported <= %d)", p->S, DKG_JES_MAX_SAMPLES);
-  if (p->m > DKG_MAX_OUTPUTS) return rfail(DKG_ERR_UNSUPPORTED, "m=%d outputs (supported <= %d)", p->m, DKG_MAX_OUTPUTS);
-  if (p->d > DKG_MAX_DIM) return rfail(DKG_ERR_UNSUPPORTED, "d=%d (supported 1..%d)", p->d, DKG_MAX_DIM);
-  if (p->R > RFF_MAXR) return rfail(DKG_ERR_UNSUPPORTED, "R=%d features (supported <= %d)", p->R, RFF_MAXR);
-  if (!p->omega || !p->bias || !p->coef || !p->offset) return rfail(DKG_ERR_ARG, "paths: NULL pointer");
-  return DKG_OK;
-}
-
-int check_population(int P) {
-  if (P < 8 || P % 4) return rfail(DKG_ERR_ARG, "population P=%d (a multiple of 4, at least 8)", P);
-  if (P > 1024) return rfail(DKG_ERR_UNSUPPORTED, "population P=%d (supported <= 1024)", P);
-  return DKG_OK;
-}
 
 // dkg_rff_weights' workspace: the batch's factorisation flags, then per slot A, X and Phi
 struct RffWs {
@@ -524,28 +313,6 @@ RffWs rff_ws(int R, int n_max) {
   w.phi = 2 * rr;
   w.slot = 2 * rr + up256((size_t)n_max * R * sizeof(double));
   w.total = 256 + RFF_NB * w.slot;
-  return w;
-}
-
-// dkg_pareto_nsga2_paths' workspace carve
-struct PathsWs {
-  size_t x2, f2, crowd2, rank2, order, total;
-};
-PathsWs paths_ws(int S, int P, int d, int m) {
-  PathsWs w{};
-  size_t off = 0;
-  const size_t q = (size_t)S * 2 * P;
-  w.x2 = off;
-  off = up256(off + q * d * sizeof(double));
-  w.f2 = off;
-  off = up256(off + q * m * sizeof(double));
-  w.crowd2 = off;
-  off = up256(off + q * sizeof(double));
-  w.rank2 = off;
-  off = up256(off + q * sizeof(int));
-  w.order = off;
-  off = up256(off + q * sizeof(int));
-  w.total = off;
   return w;
 }
 
@@ -566,7 +333,7 @@ extern "C" {
 
 int dkg_debug_rff_gram(int mode) {
   if (mode < -1 || mode > 1) {
-    rfail(DKG_ERR_ARG, "dkg_debug_rff_gram: mode=%d (0 the MFMA tiles, 1 the VALU tiles, -1 reads)", mode);
+    failf(DKG_ERR_ARG, "dkg_debug_rff_gram: mode=%d (0 the MFMA tiles, 1 the VALU tiles, -1 reads)", mode);
     return -2;
   }
   if (mode < 0) return g_rff_gram_valu.load(std::memory_order_relaxed);
@@ -581,28 +348,28 @@ size_t dkg_rff_workspace(int R, int n_max) {
 int dkg_rff_weights(const dkg_output* outs, int m, int d, const double* const* train_y, const double* wn,
                     const double* g, const double* ub, const double* z, int max_tries, const dkg_rff_paths* paths,
                     void* work, size_t work_bytes, double* jitter_used, void* stream) {
-  int st = check_paths(paths);
+  int st = check_rff_paths(paths);
   if (st) return st;
-  if (!outs || !train_y || !wn || !ub || !z || !work) return rfail(DKG_ERR_ARG, "NULL pointer");
-  if (m != paths->m || d != paths->d) return rfail(DKG_ERR_ARG, "m=%d d=%d against paths of m=%d d=%d", m, d, paths->m, paths->d);
-  if (max_tries < 0) return rfail(DKG_ERR_ARG, "max_tries=%d", max_tries);
+  if (!outs || !train_y || !wn || !ub || !z || !work) return failf(DKG_ERR_ARG, "NULL pointer");
+  if (m != paths->m || d != paths->d) return failf(DKG_ERR_ARG, "m=%d d=%d against paths of m=%d d=%d", m, d, paths->m, paths->d);
+  if (max_tries < 0) return failf(DKG_ERR_ARG, "max_tries=%d", max_tries);
   int n_max = 1;
   bool need_g = false;
   for (int i = 0; i < m; ++i) {
     const dkg_output& o = outs[i];
-    if (o.n < 1) return rfail(DKG_ERR_ARG, "output %d: n=%d training points", i, o.n);
-    if (o.n > 1024) return rfail(DKG_ERR_UNSUPPORTED, "output %d: n=%d > 1024 training points", i, o.n);
-    if (o.kernel < DKG_MATERN12 || o.kernel > DKG_RBF) return rfail(DKG_ERR_ARG, "output %d: kernel id %d", i, o.kernel);
-    if (!o.inv_lengthscale || !o.train_x || !train_y[i]) return rfail(DKG_ERR_ARG, "output %d: NULL pointer", i);
+    if (o.n < 1) return failf(DKG_ERR_ARG, "output %d: n=%d training points", i, o.n);
+    if (o.n > 1024) return failf(DKG_ERR_UNSUPPORTED, "output %d: n=%d > 1024 training points", i, o.n);
+    if (o.kernel < DKG_MATERN12 || o.kernel > DKG_RBF) return failf(DKG_ERR_ARG, "output %d: kernel id %d", i, o.kernel);
+    if (!o.inv_lengthscale || !o.train_x || !train_y[i]) return failf(DKG_ERR_ARG, "output %d: NULL pointer", i);
     if (!(o.noise > 0.0) || !(o.outputscale > 0.0))
-      return rfail(DKG_ERR_ARG, "output %d: noise=%g outputscale=%g", i, o.noise, o.outputscale);
+      return failf(DKG_ERR_ARG, "output %d: noise=%g outputscale=%g", i, o.noise, o.outputscale);
     n_max = std::max(n_max, (int)o.n);
     need_g = need_g || o.kernel != DKG_RBF;
   }
-  if (need_g && !g) return rfail(DKG_ERR_ARG, "NULL pointer (the Gamma draws of a Matern output)");
+  if (need_g && !g) return failf(DKG_ERR_ARG, "NULL pointer (the Gamma draws of a Matern output)");
   const int S = paths->S, R = paths->R;
   const RffWs w = rff_ws(R, n_max);
-  if (work_bytes < w.total) return rfail(DKG_ERR_WORKSPACE, "workspace %zu bytes < required %zu", work_bytes, w.total);
+  if (work_bytes < w.total) return failf(DKG_ERR_WORKSPACE, "workspace %zu bytes < required %zu", work_bytes, w.total);
   hipStream_t s = (hipStream_t)stream;
   char* ws = static_cast<char*>(work);
   int* d_info = reinterpret_cast<int*>(ws + w.info);
@@ -641,12 +408,12 @@ int dkg_rff_weights(const dkg_output* outs, int m, int d, const double* const* t
     }
     int h_info[RFF_NB];
     hipLaunchKernelGGL(rff_feature_kernel, dim3((R + WAVE - 1) / WAVE, (nbmax + 15) / 16, nb), dim3(256), 0, s, b);
-    if ((st = rhip(hipGetLastError(), "rff_feature_kernel")) ||
-        (st = rhip(hipMemsetAsync(d_info, 0, RFF_NB * sizeof(int), s), "hipMemsetAsync")) ||
-        (st = rhip(launch_gram(b, nb, s), "rff_gram_kernel")) ||
-        (st = rhip(launch_cholesky_batch(pb, nb, s), "cholesky_batch")) ||
-        (st = rhip(hipMemcpyAsync(h_info, d_info, nb * sizeof(int), hipMemcpyDeviceToHost, s), "hipMemcpyAsync")) ||
-        (st = rhip(hipStreamSynchronize(s), "hipStreamSynchronize")))
+    if ((st = hip_status(hipGetLastError(), "rff_feature_kernel")) ||
+        (st = hip_status(hipMemsetAsync(d_info, 0, RFF_NB * sizeof(int), s), "hipMemsetAsync")) ||
+        (st = hip_status(launch_gram(b, nb, s), "rff_gram_kernel")) ||
+        (st = hip_status(launch_cholesky_batch(pb, nb, s), "cholesky_batch")) ||
+        (st = hip_status(hipMemcpyAsync(h_info, d_info, nb * sizeof(int), hipMemcpyDeviceToHost, s), "hipMemcpyAsync")) ||
+        (st = hip_status(hipStreamSynchronize(s), "hipStreamSynchronize")))
       return st;
     // dkg_prepare_outputs' policy: the problems that failed are retried one by one with absolute jitter 1e-8 * 10^i
     for (int j = 0; j < nb; ++j) {
@@ -661,116 +428,34 @@ int dkg_rff_weights(const dkg_output* outs, int m, int d, const double* const* t
       for (int attempt = 1; attempt <= max_tries && hi != 0; ++attempt) {
         const double jit = 1e-8 * std::pow(10.0, attempt - 1);
         one.diag[0] = b.o[j].noise + jit;
-        if ((st = rhip(launch_gram(one, 1, s), "rff_gram_kernel")) ||
-            (st = rhip(hipMemsetAsync(d_info + j, 0, sizeof(int), s), "hipMemsetAsync")) ||
-            (st = rhip(launch_cholesky(b.A[j], pb.X[j], R, d_info + j, s), "cholesky")) ||
-            (st = rhip(hipMemcpyAsync(&hi, d_info + j, sizeof(int), hipMemcpyDeviceToHost, s), "hipMemcpyAsync")) ||
-            (st = rhip(hipStreamSynchronize(s), "hipStreamSynchronize")))
+        if ((st = hip_status(launch_gram(one, 1, s), "rff_gram_kernel")) ||
+            (st = hip_status(hipMemsetAsync(d_info + j, 0, sizeof(int), s), "hipMemsetAsync")) ||
+            (st = hip_status(launch_cholesky(b.A[j], pb.X[j], R, d_info + j, s), "cholesky")) ||
+            (st = hip_status(hipMemcpyAsync(&hi, d_info + j, sizeof(int), hipMemcpyDeviceToHost, s), "hipMemcpyAsync")) ||
+            (st = hip_status(hipStreamSynchronize(s), "hipStreamSynchronize")))
           return st;
         if (hi == 0 && jitter_used) jitter_used[q0 + j] = jit;
       }
       if (hi != 0)
-        return rfail(DKG_ERR_NOT_PD, "sample %d output %d: Phi^T Phi + noise I not positive definite after %d jitter "
+        return failf(DKG_ERR_NOT_PD, "sample %d output %d: Phi^T Phi + noise I not positive definite after %d jitter "
                      "retries (pivot %d)", (q0 + j) / m, (q0 + j) % m, max_tries, hi);
     }
-    if ((st = rhip(launch_tri_inverse_batch(pb, nb, s), "tri_inverse_batch"))) return st;
+    if ((st = hip_status(launch_tri_inverse_batch(pb, nb, s), "tri_inverse_batch"))) return st;
     hipLaunchKernelGGL(rff_theta_kernel, dim3(nb), dim3(1024), 0, s, b);
-    if ((st = rhip(hipGetLastError(), "rff_theta_kernel"))) return st;
+    if ((st = hip_status(hipGetLastError(), "rff_theta_kernel"))) return st;
   }
   return DKG_OK;
 }
 
 int dkg_rff_eval(const dkg_rff_paths* paths, const double* x, int P, int shared_x, double* F, void* stream) {
-  int st = check_paths(paths);
+  int st = check_rff_paths(paths);
   if (st) return st;
-  if (P < 0 || P > (1 << 24)) return rfail(DKG_ERR_ARG, "P=%d points", P);
+  if (P < 0 || P > (1 << 24)) return failf(DKG_ERR_ARG, "P=%d points", P);
   if (P == 0) return DKG_OK;
-  if (!x || !F) return rfail(DKG_ERR_ARG, "NULL pointer");
-  EvalArgs a{*paths, x, shared_x ? 0 : (size_t)P * paths->d, F, (size_t)P * paths->m, nullptr, nullptr, P};
-  return rhip(launch_eval(a, (hipStream_t)stream), "rff_eval_kernel");
-}
-
-size_t dkg_pareto_paths_workspace(int S, int P, int d, int m) {
-  if (S < 1 || S > DKG_JES_MAX_SAMPLES || P < 8 || P % 4 || P > 1024 || d < 1 || d > DKG_MAX_DIM || m < 1 ||
-      m > DKG_MAX_OUTPUTS)
-    return 0;
-  return paths_ws(S, P, d, m).total;
-}
-
-int dkg_pareto_nsga2_paths(const dkg_rff_paths* paths, const double* lb, const double* ub, int P, int gens,
-                           const dkg_nsga2_params* prm, const double* uniforms, double* X, double* F, int* rank,
-                           double* crowd, void* work, size_t work_bytes, void* stream) {
-  int st = check_paths(paths);
-  if (st) return st;
-  if ((st = check_population(P))) return st;
-  if (gens < 0 || gens > (1 << 20)) return rfail(DKG_ERR_ARG, "gens=%d generations", gens);
-  if (!prm) return rfail(DKG_ERR_ARG, "NULL pointer");
-  if (!(prm->cr >= 0.0 && prm->cr <= 1.0) || !(prm->m >= 0.0 && prm->m <= 1.0) || !(prm->eta_c >= 0.0) ||
-      !(prm->eta_m >= 0.0))
-    return rfail(DKG_ERR_ARG, "nsga2 parameters cr=%g eta_c=%g m=%g eta_m=%g", prm->cr, prm->eta_c, prm->m, prm->eta_m);
-  if (!lb || !ub || !uniforms || !X || !F || !rank || !crowd || !work) return rfail(DKG_ERR_ARG, "NULL pointer");
-  const int S = paths->S, d = paths->d, m = paths->m;
-  const PathsWs w = paths_ws(S, P, d, m);
-  if (work_bytes < w.total) return rfail(DKG_ERR_WORKSPACE, "workspace %zu bytes < required %zu", work_bytes, w.total);
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(work);
-  const size_t draws = dkg_pareto_draws(P, d);
-  PathsGen g{};
-  g.lb = lb;
-  g.ub = ub;
-  g.u = uniforms;
-  g.u_stride = (size_t)P * d + (size_t)gens * draws;
-  g.X = X;
-  g.F = F;
-  g.crowd = crowd;
-  g.rank = rank;
-  g.X2 = reinterpret_cast<double*>(ws + w.x2);
-  g.F2 = reinterpret_cast<double*>(ws + w.f2);
-  g.crowd2 = reinterpret_cast<double*>(ws + w.crowd2);
-  g.rank2 = reinterpret_cast<int*>(ws + w.rank2);
-  g.order = reinterpret_cast<int*>(ws + w.order);
-  g.P = P;
-  g.d = d;
-  g.m = m;
-  g.cr = prm->cr;
-  g.eta_c = prm->eta_c;
-  g.pm = prm->m;
-  g.eta_m = prm->eta_m;
-  const bool raw = prm->raw_inputs != 0;
-  const int Pd = P * d;
-  const dim3 b256(256);
-  EvalArgs e0{*paths, X, (size_t)Pd, F, (size_t)P * m, raw ? nullptr : lb, raw ? nullptr : ub, P};
-  hipLaunchKernelGGL(paths_init_kernel, dim3((Pd + 255) / 256, S), b256, 0, s, g);
-  if ((st = rhip(hipGetLastError(), "paths_init_kernel")) || (st = rhip(launch_eval(e0, s), "rff_eval_kernel")) ||
-      (st = rhip(launch_paths_rank(F, S, P, m, P, rank, crowd, g.order, s), "paths_rank_kernel")))
-    return st;
-  EvalArgs ec{*paths, g.X2 + Pd, 2 * (size_t)Pd, g.F2 + (size_t)P * m, 2 * (size_t)P * m, raw ? nullptr : lb,
-              raw ? nullptr : ub, P};
-  const int vt = std::max(P / 2 * d, 1), gt = P * (d + m + 2);
-  for (int gen = 0; gen < gens; ++gen) {
-    g.u_off = (size_t)Pd + (size_t)gen * draws;
-    hipLaunchKernelGGL(paths_variation_kernel, dim3((vt + 255) / 256, S), b256, 0, s, g);
-    if ((st = rhip(hipGetLastError(), "paths_variation_kernel")) || (st = rhip(launch_eval(ec, s), "rff_eval_kernel")) ||
-        (st = rhip(launch_paths_rank(g.F2, S, 2 * P, m, P, g.rank2, g.crowd2, g.order, s), "paths_rank_kernel")))
-      return st;
-    hipLaunchKernelGGL(paths_gather_kernel, dim3((gt + 255) / 256, S), b256, 0, s, g);
-    if ((st = rhip(hipGetLastError(), "paths_gather_kernel"))) return st;
-  }
-  return DKG_OK;
-}
-
-int dkg_pareto_prune(const double* F, const int* rank, int S, int Q, int m, int k, int* count, int* index,
-                     void* stream) {
-  if (S < 1 || Q < 1 || m < 1 || k < 1) return rfail(DKG_ERR_ARG, "S=%d Q=%d m=%d k=%d", S, Q, m, k);
-  if (S > DKG_JES_MAX_SAMPLES) return rfail(DKG_ERR_UNSUPPORTED, "S=%d samples (supported <= %d)", S, DKG_JES_MAX_SAMPLES);
-  if (Q > PR_MAXQ || k > PR_MAXQ) return rfail(DKG_ERR_UNSUPPORTED, "Q=%d k=%d (supported <= %d)", Q, k, PR_MAXQ);
-  if (m > DKG_MAX_OUTPUTS) return rfail(DKG_ERR_UNSUPPORTED, "m=%d objectives (supported <= %d)", m, DKG_MAX_OUTPUTS);
-  if (!F || !rank || !count || !index) return rfail(DKG_ERR_ARG, "NULL pointer");
-  const size_t lds = prune_lds_bytes(Q, m);
-  raise_lds_limit(reinterpret_cast<const void*>(pareto_prune_kernel), lds);
-  hipLaunchKernelGGL(pareto_prune_kernel, dim3(S), dim3(rank_threads(Q)), lds, (hipStream_t)stream, F, rank, Q, m, k,
-                     count, index);
-  return rhip(hipGetLastError(), "pareto_prune_kernel");
+  if (!x || !F) return failf(DKG_ERR_ARG, "NULL pointer");
+  return hip_status(launch_rff_eval(*paths, x, shared_x ? 0 : (size_t)P * paths->d, F, (size_t)P * paths->m, nullptr,
+                                    nullptr, P, (hipStream_t)stream),
+                    "rff_eval_kernel");
 }
 
 }  // extern "C"

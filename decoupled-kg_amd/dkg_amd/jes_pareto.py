@@ -1,4 +1,4 @@
-"""The Pareto samples of joint entropy search, on the device (``csrc/dkg_rff.hip``).
+"""The Pareto samples of joint entropy search, on the device (``csrc/dkg_rff.hip``, ``csrc/dkg_pareto.hip``).
 
 The reference's ``modules/pareto/jes_sample_pareto.py``: per sample a posterior path of the model drawn with random
 Fourier features (BoTorch's ``get_gp_samples``, ``:81-86``), pymoo's NSGA-II on the path (``:146-207``) and the
@@ -32,7 +32,7 @@ from . import _lib
 from .errors import UnsupportedError
 from .gp_state import _base_struct, current_stream_ptr
 from .model import ModelListGPState, SingleTaskGPState
-from .pareto import _dev_vec, _device, pareto_draws
+from .pareto import _device, _evolve, pareto_draws
 
 # the reference's variation (jes_sample_pareto.py:200-201): SimulatedBinaryCrossover(prob=0.9, eta=15),
 # PolynomialMutation(eta=20); the per-coordinate mutation probability is pymoo's default, min(0.5, 1 / d)
@@ -168,28 +168,10 @@ def pareto_nsga2_paths(paths: RffPaths, lb, ub, P: int, gens: int, uniforms, raw
     """``dkg_pareto_nsga2_paths``: population s evolves on sample s -> (X [S, P, d], F [S, P, m], rank [S, P],
     crowd [S, P]) device tensors.  ``uniforms``: [S, P d + gens * pareto_draws(P, d)] doubles in [0, 1).  ``m``: the
     per-coordinate mutation probability (None: ``min(0.5, 1 / d)``)."""
-    dev, S, d, mo = paths.device, paths.S, paths.d, paths.m
-    lb, ub = _dev_vec(lb, dev, d), _dev_vec(ub, dev, d)
-    P, gens = int(P), int(gens)
-    lib = _lib.load()
-    per = P * d + gens * int(lib.dkg_pareto_draws(P, d))
-    uniforms = torch.as_tensor(uniforms, dtype=torch.double).to(dev).contiguous()
-    if lib.dkg_pareto_draws(P, d) and tuple(uniforms.shape) != (S, per):
-        raise ValueError(f"uniforms of shape {tuple(uniforms.shape)}, expected {(S, per)}")
-    pm = min(0.5, 1.0 / d) if m is None else float(m)
-    X = torch.empty(S, max(P, 0), d, dtype=torch.double, device=dev)
-    F = torch.empty(S, max(P, 0), mo, dtype=torch.double, device=dev)
-    rank = torch.empty(S, max(P, 0), dtype=torch.int32, device=dev)
-    crowd = torch.empty(S, max(P, 0), dtype=torch.double, device=dev)
-    nbytes = int(lib.dkg_pareto_paths_workspace(S, P, d, mo))
-    work = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    pm = min(0.5, 1.0 / paths.d) if m is None else float(m)
     prm = _lib.DkgNsga2Params(cr, eta_c, pm, eta_m, raw_inputs=1 if raw_inputs else 0)
-    with torch.cuda.device(dev):
-        _lib.check(lib.dkg_pareto_nsga2_paths(paths.struct(), _lib.ptr(lb), _lib.ptr(ub), P, gens, prm,
-                                              _lib.ptr(uniforms), _lib.ptr(X), _lib.ptr(F), _lib.ptr(rank),
-                                              _lib.ptr(crowd), _lib.ptr(work), nbytes, current_stream_ptr(dev)),
-                   "dkg_pareto_nsga2_paths")
-    return X, F, rank, crowd
+    return _evolve("dkg_pareto_nsga2_paths", (paths.struct(),), "dkg_pareto_paths_workspace", paths.device,
+                   (paths.S,), paths.d, paths.m, lb, ub, P, gens, uniforms, prm)
 
 
 def pareto_prune(F, rank, k: int):

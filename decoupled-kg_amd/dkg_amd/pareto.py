@@ -166,25 +166,38 @@ def pareto_nsga2(model, lb, ub, P: int, gens: int, uniforms, raw_inputs: bool = 
     device tensors.  ``uniforms``: ``P d + gens * pareto_draws(P, d)`` doubles in [0, 1).  ``raw_inputs``: the model
     takes the points as they are (a test problem) instead of normalised with the bounds (a surrogate)."""
     pm = _prepared(model, device)
-    dev, d, mo = pm.device, pm.d, pm.m
+    prm = _lib.DkgNsga2Params(cr, eta_c, m, eta_m, raw_inputs=1 if raw_inputs else 0)
+    return _evolve("dkg_pareto_nsga2", (pm.structs, pm.m, pm.d), "dkg_pareto_workspace", pm.device, (), pm.d, pm.m,
+                   lb, ub, P, gens, uniforms, prm)
+
+
+def _evolve(entry: str, model_args: tuple, workspace: str, dev, lead: tuple, d: int, mo: int, lb, ub, P, gens,
+            uniforms, prm):
+    """One call of an evolution entry (``dkg_pareto_nsga2``: ``lead = ()``, one population and at least the
+    uniforms it reads; ``dkg_pareto_nsga2_paths``: ``lead = (S,)``, uniforms of exactly ``[S, per sample]``) ->
+    (X ``lead + [P, d]``, F ``lead + [P, m]``, rank, crowd ``lead + [P]``) device tensors.  ``model_args``: the
+    entry's leading arguments; ``workspace``: the entry's workspace query, called with ``lead + (P, d, m)``."""
     lb, ub = _dev_vec(lb, dev, d), _dev_vec(ub, dev, d)
     uniforms = torch.as_tensor(uniforms, dtype=torch.double).to(dev).contiguous()
     P, gens = int(P), int(gens)
     lib = _lib.load()
-    need = P * d + gens * int(lib.dkg_pareto_draws(P, d))
-    if lib.dkg_pareto_draws(P, d) and uniforms.numel() < need:
+    draws = int(lib.dkg_pareto_draws(P, d))  # 0 for a P the entry refuses: the call below reports it
+    need = P * d + gens * draws
+    if draws and lead and tuple(uniforms.shape) != lead + (need,):
+        raise ValueError(f"uniforms of shape {tuple(uniforms.shape)}, expected {lead + (need,)}")
+    if draws and not lead and uniforms.numel() < need:
         raise ValueError(f"{uniforms.numel()} uniforms < {need}")
-    X = torch.empty(max(P, 0), d, dtype=torch.double, device=dev)
-    F = torch.empty(max(P, 0), mo, dtype=torch.double, device=dev)
-    rank = torch.empty(max(P, 0), dtype=torch.int32, device=dev)
-    crowd = torch.empty(max(P, 0), dtype=torch.double, device=dev)
-    nbytes = int(lib.dkg_pareto_workspace(P, d, mo))
+    rows = lead + (max(P, 0),)
+    X = torch.empty(*rows, d, dtype=torch.double, device=dev)
+    F = torch.empty(*rows, mo, dtype=torch.double, device=dev)
+    rank = torch.empty(*rows, dtype=torch.int32, device=dev)
+    crowd = torch.empty(*rows, dtype=torch.double, device=dev)
+    nbytes = int(getattr(lib, workspace)(*lead, P, d, mo))
     work = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
-    prm = _lib.DkgNsga2Params(cr, eta_c, m, eta_m, raw_inputs=1 if raw_inputs else 0)
     with torch.cuda.device(dev):
-        _lib.check(lib.dkg_pareto_nsga2(pm.structs, mo, d, _lib.ptr(lb), _lib.ptr(ub), P, gens, prm,
-                                        _lib.ptr(uniforms), _lib.ptr(X), _lib.ptr(F), _lib.ptr(rank), _lib.ptr(crowd),
-                                        _lib.ptr(work), nbytes, current_stream_ptr(dev)), "dkg_pareto_nsga2")
+        _lib.check(getattr(lib, entry)(*model_args, _lib.ptr(lb), _lib.ptr(ub), P, gens, prm, _lib.ptr(uniforms),
+                                       _lib.ptr(X), _lib.ptr(F), _lib.ptr(rank), _lib.ptr(crowd), _lib.ptr(work),
+                                       nbytes, current_stream_ptr(dev)), entry)
     return X, F, rank, crowd
 
 

@@ -275,7 +275,9 @@ int dkg_pareto_variation(const double* X, const int* rank, const double* crowd, 
                          void* stream);
 
 /* Bytes of device scratch dkg_pareto_nsga2 needs (0 outside the limits above); it includes
- * dkg_pareto_rank_workspace(2P, m), so its ranks follow dkg_pareto_rank's rule with a workspace. */
+ * dkg_pareto_rank_workspace(2P, m), so its ranks follow dkg_pareto_rank's rule with a workspace.  The posterior-mean
+ * kernel normalises the points itself, so there is no section for normalised points: the value is smaller, by
+ * P d doubles rounded up to 256 bytes, than the first libraries of this ABI version returned. */
 size_t dkg_pareto_workspace(int P, int d, int m);
 
 /* The whole evolution, no host synchronisation inside: what pop = algo.evolve(pop) does at sample.py:40-44.
@@ -416,10 +418,11 @@ int dkg_rff_eval(const dkg_rff_paths* paths, const double* x, int P, int shared_
 /* Bytes of device scratch dkg_pareto_nsga2_paths needs (0 outside the limits). */
 size_t dkg_pareto_paths_workspace(int S, int P, int d, int m);
 
-/* dkg_pareto_nsga2 for S populations at once, population s evolving on sample s of `paths`: every launch carries a
- * sample axis (init; then per generation the variation, which also copies the parents; dkg_rff_eval of the children;
- * the one-workgroup rank of the 2P points, one workgroup per sample; the gather).  Four launches per generation
- * whatever S is, no host synchronisation.
+/* dkg_pareto_nsga2 for S populations at once, population s evolving on sample s of `paths`.  It is the same
+ * generation driver with the paths as its fitness (dkg_pareto.hip: dkg_pareto_nsga2 is its S = 1 case on the
+ * posterior mean, with the wide rank's scratch): every launch carries a sample axis (init; then per generation the
+ * variation, which also copies the parents; dkg_rff_eval of the children; the one-workgroup rank of the 2P points,
+ * one workgroup per sample; the gather).  Four launches per generation whatever S is, no host synchronisation.
  *   uniforms: device [S][P d + gens * dkg_pareto_draws(P, d)], sample s's row laid out as dkg_pareto_nsga2's
  *   lb, ub  : device [d], shared by the samples; the path takes (x - lb) / (ub - lb) unless prm->raw_inputs
  *   X [S][P][d], F [S][P][m], rank [S][P], crowd [S][P]: device, the final populations and their rankings

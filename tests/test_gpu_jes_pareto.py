@@ -152,7 +152,7 @@ def test_eval_bits_do_not_depend_on_the_batch(S, m, d, R):
 
 # ---------------------------------------------------------------- generations
 
-GEN_SHAPES = [(3, 8, 1, 1), (3, 12, 2, 2), (2, 64, 3, 3), (3, 100, 2, 2)]  # S, P, d, m
+GEN_SHAPES = [(3, 8, 1, 1), (3, 12, 2, 2), (2, 64, 3, 3), (3, 100, 2, 2), (1, 8, 5, 2)]  # S, P, d, m
 PRM = dict(cr=0.9, eta_c=15.0, eta_m=20.0)
 
 

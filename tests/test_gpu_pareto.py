@@ -199,7 +199,8 @@ def test_variation_against_the_restatement(P, d):
 
 # ---------------------------------------------------------------- one generation, the whole call
 
-GEN_SHAPES = [(8, 1, 1), (12, 2, 2), (64, 3, 3), (1024, 16, 8)]
+# (12, 5, 2) and (8, 9, 1): d below its bucket of 8 / 16, where the fused normalisation's clamped coordinate is live
+GEN_SHAPES = [(8, 1, 1), (12, 2, 2), (64, 3, 3), (1024, 16, 8), (12, 5, 2), (8, 9, 1)]
 GEN_NS = (20, 31, 16, 45, 27, 38, 18, 52)
 
 

@@ -338,6 +338,44 @@ def test_pareto_workspace_and_draws_grow():
     assert w(6, 2, 2) == 0 and w(1028, 2, 2) == 0 and w(8, 17, 2) == 0 and w(8, 2, 9) == 0
 
 
+def test_evolution_entries_share_their_argument_checks():
+    """dkg_pareto_variation, dkg_pareto_nsga2 and dkg_pareto_nsga2_paths refuse the same bad argument with the same
+    status, before any device call; the workspace queries against the values of the commit before the one driver
+    (recorded from its library): the paths' unchanged, the single population's less its normalised-points section."""
+    lib = _lib.load()
+    ptr, good = 16, _lib.DkgNsga2Params()
+    paths = _lib.DkgRffPaths(2, 2, 2, 64, ptr, ptr, ptr, ptr)
+    outs = _outs()
+
+    def variation(P=8, prm=good):
+        return lib.dkg_pareto_variation(ptr, ptr, ptr, P, 2, ptr, ptr, prm, ptr, ptr, None)
+
+    def nsga2(P=8, prm=good, gens=1, short=0):
+        work = (lib.dkg_pareto_workspace(P, 2, 2) or 1 << 30) - short
+        return lib.dkg_pareto_nsga2(outs, 2, 2, ptr, ptr, P, gens, prm, ptr, ptr, ptr, ptr, ptr, ptr, work, None)
+
+    def nsga2_paths(P=8, prm=good, gens=1, short=0):
+        work = (lib.dkg_pareto_paths_workspace(2, P, 2, 2) or 1 << 30) - short
+        return lib.dkg_pareto_nsga2_paths(paths, ptr, ptr, P, gens, prm, ptr, ptr, ptr, ptr, ptr, ptr, work, None)
+
+    every, evolutions = (variation, nsga2, nsga2_paths), (nsga2, nsga2_paths)
+    table = [(every, dict(P=6), _lib.DKG_ERR_ARG), (every, dict(P=10), _lib.DKG_ERR_ARG),
+             (every, dict(P=1028), _lib.DKG_ERR_UNSUPPORTED),
+             (every, dict(prm=_lib.DkgNsga2Params(cr=1.5)), _lib.DKG_ERR_ARG),
+             (every, dict(prm=_lib.DkgNsga2Params(m=-0.1)), _lib.DKG_ERR_ARG),
+             (every, dict(prm=_lib.DkgNsga2Params(eta_c=-1.0)), _lib.DKG_ERR_ARG),
+             (every, dict(prm=None), _lib.DKG_ERR_ARG),
+             (evolutions, dict(gens=-1), _lib.DKG_ERR_ARG),
+             (evolutions, dict(short=1), _lib.DKG_ERR_WORKSPACE)]
+    for entries, bad, want in table:
+        assert [entry(**bad) for entry in entries] == [want] * len(entries), bad
+    sizes = [lib.dkg_pareto_paths_workspace(*a) for a in ((1, 8, 1, 1), (3, 100, 2, 2), (10, 1024, 16, 8))]
+    assert sizes == [1280, 29440, 4259840]
+    before = {(8, 1, 1): 2304, (100, 2, 2): 14592, (1024, 16, 8): 573696}
+    for (P, d, m), old in before.items():
+        assert lib.dkg_pareto_workspace(P, d, m) == old - (P * d * 8 + 255) // 256 * 256
+
+
 def test_front_sampler_refuses_minimisation_before_any_device_work():
     from dkg_amd import UnsupportedError, sample_points_on_pareto_front
 

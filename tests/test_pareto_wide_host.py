@@ -40,11 +40,11 @@ def test_rank_argument_checks_with_a_workspace():
 
 
 def parent_nsga2_carve(P, d, m):
-    """The carve of dkg_pareto_nsga2 before the rank scratch joined it (nsga_ws in csrc/dkg_pareto.hip)."""
+    """The carve of dkg_pareto_nsga2 without the rank scratch (gen_ws in csrc/dkg_pareto.hip, one population): the
+    evaluator normalises the points itself, so there is no section for normalised points."""
     up = lambda x: (x + 255) & ~255  # noqa: E731
     off = up(2 * P * d * 8)
     off = up(off + 2 * P * m * 8)
-    off = up(off + P * d * 8)
     off = up(off + 2 * P * 8)
     off = up(off + 2 * P * 4)
     return up(off + 2 * P * 4)

@@ -48,7 +48,7 @@ RANK_WIDE = ("pareto_clear_kernel", "pareto_dom_kernel", "pareto_peel_kernel", "
              "pareto_order_kernel")
 STAGES = {"posterior_mean": ("posterior_mean_kernel",), "rank": ("pareto_rank_kernel",) + RANK_WIDE,
           "variation": ("pareto_variation_kernel",),
-          "glue": ("pareto_init_kernel", "pareto_normalise_kernel", "pareto_gather_kernel")}
+          "glue": ("pareto_init_kernel", "pareto_gather_kernel")}
 BOUNDS = torch.tensor([[0.0, 0.0], [1.0, 1.0]], dtype=torch.double)
 OUT_DIR = os.path.join(REPO, "profiles", "pareto_wide")
 SWEEP_Q = (8, 16, 32, 64, 128, 200, 256, 512, 1024, 2000, 2048)
