@@ -25,6 +25,7 @@ from .gp_state import (
     set_incremental_state,
     state_stats,
 )
+from .hvkg import PosteriorMeanHypervolume, qHypervolumeKnowledgeGradient
 from .jes import compute_sample_box_decomposition, qLowerBoundMultiObjectiveJointEntropySearch
 from .jes_pareto import sample_discrete_pareto_optimal_points, sample_rff_paths
 from .metrics import (
@@ -49,6 +50,8 @@ __all__ = [
     "kg_from_lines",
     "qLowerBoundMultiObjectiveJointEntropySearch",
     "compute_sample_box_decomposition",
+    "qHypervolumeKnowledgeGradient",
+    "PosteriorMeanHypervolume",
     "normalise_targets",
     "t_batch_mode_transform",
     "BotorchTensorDimensionError",

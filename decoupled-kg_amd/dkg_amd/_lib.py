@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_size_t, c_uint, c_void_p
 
 from .errors import BotorchTensorDimensionError, DkgNativeError, NotPSDError, UnsupportedError
 
@@ -32,6 +32,8 @@ MAX_OUTPUTS = 8
 MAX_DIM = 16
 # include/dkg.h: the limits of the joint entropy search plan (dkg_jes_init)
 DKG_JES_MAX_SAMPLES, DKG_JES_MAX_BOXES, DKG_JES_MAX_CANDIDATES = 64, 4096, 65536
+# include/dkg.h: the limits of the hypervolume knowledge gradient plan (dkg_hvkg_init)
+DKG_HVKG_MAX_FANTASIES, DKG_HVKG_MAX_PARETO, DKG_HVKG_MAX_RESTARTS = 64, 32, 4096
 
 (DKG_OK, DKG_ERR_ARG, DKG_ERR_UNSUPPORTED, DKG_ERR_WORKSPACE, DKG_ERR_HIP, DKG_ERR_NO_LINES,
  DKG_ERR_NOT_PD) = range(7)
@@ -107,6 +109,12 @@ SIGNATURES = {
     "dkg_jes_init": (c_int, [POINTER(DkgOutput), c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                              c_size_t, c_void_p, c_void_p]),
     "dkg_jes_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dkg_hvkg_plan_bytes": (c_size_t, []),
+    "dkg_hvkg_workspace": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "dkg_hvkg_init": (c_int, [POINTER(DkgOutput), c_int, c_int, POINTER(c_double), c_int, c_int, POINTER(c_double),
+                              c_uint, c_double, c_double, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "dkg_hvkg_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dkg_hypervolume": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_double), c_void_p, c_void_p, c_void_p]),
     "dkg_abi_version": (c_int, []),
     "dkg_last_error": (c_char_p, []),
     "dkg_frag_elems": (c_size_t, [c_int, c_int]),

@@ -21,7 +21,8 @@ candidates (``pipeline/nodes/bo_loop.py:127-129``).  ``batch_limit`` keeps BoTor
 restarts in one chunk share one L-BFGS-B problem (the sum of their values).
 
 ``JesOptimisationSpec`` (``acquisition_optimisation_strategy.py:447-552``) runs the same ``optimize_acqf`` on
-the device joint entropy search (``dkg_amd.jes``).
+the device joint entropy search (``dkg_amd.jes``), and ``HvkgOptimisationSpec`` (``:276-444``) on the
+device hypervolume knowledge gradient (``dkg_amd.hvkg``).
 """
 
 from __future__ import annotations
@@ -139,10 +140,11 @@ def optimize_acqf(acq_function: Callable[[Tensor], Tensor], bounds: Tensor, q: i
                   raw_samples: Optional[int] = None, options: Optional[Dict] = None,
                   batch_initial_conditions: Optional[Tensor] = None,
                   return_best_only: bool = True) -> Tuple[Tensor, Tensor]:
-    """``botorch.optim.optimize_acqf`` for the q = 1 / no-constraint case the reference uses
-    (``acquisition_optimisation_strategy.py:217-224, 259-266``)."""
-    if q != 1:
-        raise NotImplementedError("only q = 1 is supported (DiscreteKnowledgeGradient is q = 1)")
+    """``botorch.optim.optimize_acqf`` for the no-constraint, non-sequential case the reference uses: q = 1
+    (``acquisition_optimisation_strategy.py:217-224, 259-266``) and the joint optimisation of a q-batch
+    (``:435-443``; every restart is a ``q x d`` point, and the initialiser and ``gen_candidates_scipy`` take any q)."""
+    if q < 1:
+        raise ValueError(f"q must be at least 1, got {q}")
     options = dict(options or {})
     if batch_initial_conditions is None:
         if raw_samples is None:
@@ -449,3 +451,114 @@ class JesOptimisationSpec:
         return candidate_x.detach(), acq_value.detach()
 
     _choose_best_objective = staticmethod(DiscreteKgOptimisationSpec._choose_best_objective)
+
+
+class HvkgOptimisationSpec:
+    """``HvkgOptimisationSpec`` (``acquisition_optimisation_strategy.py:276-444``) on the device hypervolume
+    knowledge gradient: the reference's constructor arguments, its two entry points with their ``hv_refpoint``
+    keyword and their warnings.  The decoupled decision is the argmax of the per-objective values: the cost is
+    inside the acquisition (its cost-aware utility), so it is not ``_choose_best_objective`` (:382-386).
+
+    The current optimum is the best value of the value function (``PosteriorMeanHypervolume``) over
+    ``q = num_pareto`` points (``_compute_current_optimum``, :428-444).
+
+    One-shot initial conditions are this library's own (BoTorch's ``gen_one_shot_hvkg_initial_conditions`` is
+    absent, so parity with it is unpinned): ``raw_samples`` Sobol candidates, each with the current
+    optimum's Pareto set repeated over the fantasies as its fantasy rows, evaluated without gradient in chunks,
+    ``num_restarts`` of them picked by ``initialize_q_batch``; L-BFGS-B then moves every row of the one-shot
+    points inside the unit cube, and the candidate returned is ``extract_candidates`` of the best restart.
+
+    ``acq_factory(kind, model, ref_point, **kwargs)`` (tests inject a CPU restatement): ``kind`` is
+    ``"value_function"`` (no kwargs) or ``"hvkg"`` (``num_fantasies``, ``num_pareto``, ``current_value``,
+    ``cost_aware_utility``, ``seed``); ``None`` builds the device acquisitions."""
+
+    INIT_CHUNK = 512  # one-shot points per evaluation of the raw-sample screen
+
+    def __init__(self, num_pareto: int, num_fantasies: int, num_restarts: int, raw_samples: int,
+                 curr_opt_num_restarts: int, curr_opt_raw_samples: int, batch_limit: int, max_iter: int, device=None,
+                 seed: Optional[int] = None, acq_factory: Optional[Callable] = None):
+        self.num_pareto = num_pareto
+        self.num_fantasies = num_fantasies
+        self.num_restarts = num_restarts
+        self.raw_samples = raw_samples
+        self.curr_opt_num_restarts = curr_opt_num_restarts
+        self.curr_opt_raw_samples = curr_opt_raw_samples
+        self.batch_limit = batch_limit
+        self.max_iter = max_iter
+        self.device = device
+        self.seed = seed
+        self.acq_factory = acq_factory
+
+    def _seeded(self, opts: Dict) -> Dict:
+        if self.seed is not None:
+            opts["seed"] = self.seed
+        return opts
+
+    def _value_function(self, model, ref_point):
+        if self.acq_factory is not None:
+            return self.acq_factory("value_function", model, ref_point)
+        from .hvkg import PosteriorMeanHypervolume
+
+        return PosteriorMeanHypervolume(model, ref_point, device=self.device)
+
+    def _acq(self, model, ref_point, current_value, costs):
+        kw = dict(num_fantasies=self.num_fantasies, num_pareto=self.num_pareto, current_value=current_value,
+                  cost_aware_utility=costs, seed=self.seed)
+        if self.acq_factory is not None:
+            return self.acq_factory("hvkg", model, ref_point, **kw)
+        from .hvkg import qHypervolumeKnowledgeGradient
+
+        return qHypervolumeKnowledgeGradient(model, ref_point, device=self.device, **kw)
+
+    def _compute_current_optimum(self, model, ref_point, bounds) -> Tuple[Tensor, Tensor]:
+        """The hypervolume-maximising set of ``num_pareto`` points under the posterior mean and its hypervolume."""
+        pareto_set, current_optimum = optimize_acqf(
+            acq_function=self._value_function(model, ref_point), bounds=bounds, q=self.num_pareto,
+            num_restarts=self.curr_opt_num_restarts, raw_samples=self.curr_opt_raw_samples,
+            options=self._seeded({"batch_limit": self.batch_limit}))
+        return pareto_set.detach(), current_optimum.detach()
+
+    def _optimize_one_shot(self, acq_func, bounds: Tensor, pareto_set: Tensor) -> Tuple[Tensor, Tensor]:
+        candidates = draw_sobol_samples(bounds, self.raw_samples, 1, seed=self.seed)            # [raw, 1, d]
+        fantasy_rows = pareto_set.to(candidates).repeat(self.num_fantasies, 1)                  # [Nf Np, d]
+        X_raw = torch.cat([candidates, fantasy_rows.expand(self.raw_samples, -1, -1)], dim=1)
+        Y_raw = _no_grad_values(acq_func, X_raw, self.INIT_CHUNK)
+        ic = initialize_q_batch(X_raw, Y_raw.to(X_raw), n=self.num_restarts)
+        X_full, acq_value = optimize_acqf(acq_function=acq_func, bounds=bounds, q=X_raw.shape[1],
+                                          num_restarts=self.num_restarts, batch_initial_conditions=ic,
+                                          options={"batch_limit": self.batch_limit, "maxiter": self.max_iter})
+        return acq_func.extract_candidates(X_full).detach(), acq_value.detach()
+
+    def optimize_for_single_objective(self, model, costs: Union[Tensor, Sequence], input_dim: int, *,
+                                      hv_refpoint: Tensor, **_unused_kwargs) -> Tuple[Tensor, int, Tensor]:
+        """One mask per objective on one acquisition, the best value wins (:322-388)."""
+        from .discretekg import _as_model_state
+
+        bounds = _get_standard_bounds(input_dim)
+        pareto_set, current_opt = self._compute_current_optimum(model, hv_refpoint, bounds)
+        m = _as_model_state(model).num_outputs
+        acq_func = self._acq(model, hv_refpoint, current_opt, [float(c) for c in torch.as_tensor(costs).reshape(-1)])
+        objective_candidates, objective_vals = [], []
+        for i in range(m):
+            evaluation_mask = torch.zeros(1, m, dtype=torch.bool)
+            evaluation_mask[0, i] = 1
+            acq_func.X_evaluation_mask = evaluation_mask
+            candidate_x, acq_value = self._optimize_one_shot(acq_func, bounds, pareto_set)
+            if acq_value <= 0:
+                logger.warning("Optimal acquisition function value is not strictly positive "
+                               "(after clipping to be at least zero): obj_index=%i, acq_value=%f", i, acq_value)
+            objective_candidates.append(candidate_x)
+            objective_vals.append(acq_value)
+        best_i = int(torch.stack(objective_vals).argmax().item())
+        return objective_candidates[best_i], best_i, objective_vals[best_i]
+
+    def optimize_for_full_evaluation(self, model, input_dim: int, *, hv_refpoint: Tensor,
+                                     **_unused_kwargs) -> Tuple[Tensor, Tensor]:
+        """Every output observed, no cost-aware utility (:390-426)."""
+        bounds = _get_standard_bounds(input_dim)
+        pareto_set, current_opt = self._compute_current_optimum(model, hv_refpoint, bounds)
+        acq_func = self._acq(model, hv_refpoint, current_opt, None)
+        candidate_x, acq_value = self._optimize_one_shot(acq_func, bounds, pareto_set)
+        if acq_value < 0:
+            logger.warning("Optimal acquisition function value is negative: acq_value=%f", acq_value)
+        return candidate_x, acq_value

@@ -42,7 +42,7 @@ extern "C" {
 #define DKG_ABI_VERSION 9  /* 9: dkg_append_observation; 8: dkg_plan_forward_batches, dkg_plan_time_stage_batches */
 /* Added under 9 since (new symbols only; nothing that existed changed): dkg_mll_*, dkg_posterior_mean, dkg_pareto_*,
  * dkg_jes_*, dkg_rff_workspace, dkg_rff_weights, dkg_rff_eval, dkg_debug_rff_gram, dkg_pareto_paths_workspace,
- * dkg_pareto_nsga2_paths, dkg_pareto_prune. */
+ * dkg_pareto_nsga2_paths, dkg_pareto_prune, dkg_hvkg_*, dkg_hypervolume. */
 #define DKG_MAX_OUTPUTS 8   /* outputs (objectives) per model list */
 #define DKG_MAX_DIM 16      /* input dimension d */
 
@@ -450,6 +450,68 @@ int dkg_pareto_nsga2_paths(const dkg_rff_paths* paths, const double* lb, const d
  * (tens of milliseconds).  Sized for populations, not for the 16384-point fronts of dkg_pareto_rank. */
 int dkg_pareto_prune(const double* F, const int* rank, int S, int Q, int m, int k, int* count, int* index,
                      void* stream);
+
+/* ---- Hypervolume knowledge gradient (HVKG, Daulton et al. 2023) on the device (dkg_hvkg.hip) -------------------
+ * BoTorch's qHypervolumeKnowledgeGradient as the reference's HvkgOptimisationSpec drives it
+ * (modules/acquisition_optimisation_strategy.py:276-444): q = 1, one-shot, the posterior mean as the inner value
+ * function, X_evaluation_mask for the decoupled setting, and its value function (the hypervolume of the posterior
+ * mean at q points, _compute_current_optimum :428-444).  All objectives are maximised; everything is fp64.
+ * A one-shot point is X_full [1 + Nf Np][d]: row 0 the candidate x, row 1 + f Np + p point p of fantasy f
+ * (BoTorch's layout).  Per output i, with mu_i, c_i the model-space posterior mean and covariance and
+ * sigma~_i(x) = sqrt(c_i(x, x) + noise_i):
+ *   Y_fp,i = y_mean_i + y_std_i (mu_i(x'_fp) + [i in E] z_f,i c_i(x'_fp, x) / sigma~_i(x))
+ *   HV_f   = the volume of the union over p of the boxes [ref, Y_fp]; a point that is not strictly above ref in
+ *            every objective adds nothing
+ *   acq    = ((1 / Nf) sum_f HV_f - current_value) / cost
+ * The fantasy mean is the exact posterior mean after observing mu_i(x) + sigma~_i(x) z_f,i at x with the
+ * likelihood's noise (fantasize + PosteriorMeanModel, without refactorising).  Gradient conventions at kinks
+ * (subgradients): a point that adds no volume (dominated, or not strictly above ref) gets exactly 0; of points
+ * with equal coordinates the lowest index takes the derivative.  DESIGN.md 8f.
+ * Outputs are dkg_prepare_outputs' structs (n, kernel, the hyperparameters, y_mean, y_std, inv_lengthscale,
+ * train_x, alpha and root_frag are read; disc_* are not).  Limits (DKG_ERR_UNSUPPORTED beyond them): m = 2 or 3,
+ * d <= DKG_MAX_DIM, n <= 1024, and the three below. */
+#define DKG_HVKG_MAX_FANTASIES 64
+#define DKG_HVKG_MAX_PARETO 32
+#define DKG_HVKG_MAX_RESTARTS 4096
+/* Bytes of the host plan (caller memory, kept unchanged while the plan is in use). */
+size_t dkg_hvkg_plan_bytes(void);
+/* Bytes of device scratch a plan for up to max_B restarts needs; 0 for sizes dkg_hvkg_init refuses. */
+size_t dkg_hvkg_workspace(int m, int d, int num_fantasies, int num_pareto, int max_B);
+/* A plan: everything an evaluation needs besides the one-shot points.
+ *   outs         : host array of m structs, copied into host_plan and uploaded into the workspace on `stream`
+ *   ref_point    : host [m], untransformed output space
+ *   base_samples : host [num_fantasies][m], the z_f,i (not read, nullable, when mask is 0)
+ *   mask         : bit i set = output i is evaluated at the candidate (BoTorch's X_evaluation_mask for q = 1).
+ *                  0 selects the value function: no candidate row, num_fantasies must be 1 and the input of
+ *                  dkg_hvkg_forward is X [B][num_pareto][d]
+ *   current_value, cost: the scalars of acq above (0 and 1 when absent); cost > 0
+ *   workspace    : device scratch of dkg_hvkg_workspace() bytes, owned by the plan while it is in use
+ * DKG_ERR_ARG for NULL pointers, sizes < 1, a mask with bits at or above m, an empty mask with num_fantasies != 1,
+ * a cost that is not positive, n < 1 or an unknown kernel id; DKG_ERR_UNSUPPORTED beyond the limits or for m not in
+ * {2, 3}; DKG_ERR_WORKSPACE for a short workspace.  The arguments are checked before any HIP call; nothing
+ * synchronises. */
+int dkg_hvkg_init(const dkg_output* outs, int m, int d, const double* ref_point, int num_fantasies, int num_pareto,
+                  const double* base_samples, unsigned mask, double current_value, double cost, int max_B,
+                  void* workspace, size_t workspace_bytes, void* host_plan, void* stream);
+/* acq[b] for B <= max_B one-shot points x_full (device [B][1 + Nf Np][d]; value-function mode [B][Np][d]) and, when
+ * dacq_dx is not NULL, the gradient in every entry of x_full (device, the shape of x_full), by a hand-written
+ * adjoint.  y_out (nullable): device [B][Nf][Np][m], the fantasised means Y.  Four launches (three in
+ * value-function mode) whatever B, Nf, Np and m are: the candidate's K^-1 k(X, x) and sigma~ per (restart, output
+ * in E); one wave per fantasy point for Y and dY/dx'; one wave per (restart, fantasy) for HV_f and dHV_f/dY; one
+ * workgroup per restart for acq and the gradient, which costs one more product with K^-1 per (restart, output in
+ * E), not per fantasy point.  Stream ordered, nothing synchronises, no atomics, every sum in a fixed order: two
+ * calls give the same bits, and a restart's value and gradient have the same bits whatever B is and whichever row
+ * holds it.  DKG_ERR_ARG for NULL pointers, an uninitialised plan or B outside [1, max_B], checked before any HIP
+ * call. */
+int dkg_hvkg_forward(const void* host_plan, const double* x_full, int B, double* acq, double* dacq_dx, double* y_out,
+                     void* stream);
+/* The hypervolume stage alone (the kernel dkg_hvkg_forward launches): hv[s] = the volume of the union of the boxes
+ * [ref, Y[s][p]] over the num_pareto <= DKG_HVKG_MAX_PARETO points of set s, and, when dhv is not NULL,
+ * dhv[s][p][i] = d hv[s] / d Y[s][p][i] with the conventions above.  Y, hv, dhv: device; ref_point: host [m].
+ * m = 2: a sort and one sweep; m = 3: slabs on the last objective over 2-d sweeps; every term of the value is
+ * positive.  DKG_ERR_UNSUPPORTED for m not in {2, 3} or num_pareto beyond the limit. */
+int dkg_hypervolume(const double* Y, int S, int num_pareto, int m, const double* ref_point, double* hv, double* dhv,
+                    void* stream);
 
 /* Bytes of scratch dkg_forward needs for (m outputs, N points, B candidates, S weights). */
 size_t dkg_forward_workspace(const dkg_output* outs, int m, int N, int B, int S);
