@@ -4,6 +4,7 @@ Drop-in for ``decoupledbo.modules.acquisition.discretekg``; the arithmetic runs
 in hand-written HIP kernels for gfx950 behind the C ABI of ``include/dkg.h``.
 """
 
+from .boxes import dominated_boxes, hypervolume_front
 from .discretekg import (
     DiscreteKnowledgeGradient,
     calculate_discrete_kg,
@@ -50,6 +51,8 @@ __all__ = [
     "kg_from_lines",
     "qLowerBoundMultiObjectiveJointEntropySearch",
     "compute_sample_box_decomposition",
+    "dominated_boxes",
+    "hypervolume_front",
     "qHypervolumeKnowledgeGradient",
     "PosteriorMeanHypervolume",
     "normalise_targets",

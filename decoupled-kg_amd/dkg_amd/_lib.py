@@ -34,6 +34,8 @@ MAX_DIM = 16
 DKG_JES_MAX_SAMPLES, DKG_JES_MAX_BOXES, DKG_JES_MAX_CANDIDATES = 64, 4096, 65536
 # include/dkg.h: the limits of the hypervolume knowledge gradient plan (dkg_hvkg_init)
 DKG_HVKG_MAX_FANTASIES, DKG_HVKG_MAX_PARETO, DKG_HVKG_MAX_RESTARTS = 64, 32, 4096
+# include/dkg.h: the limits of dkg_dominated_boxes and dkg_hypervolume_front
+DKG_BOXES_MAX_POINTS, DKG_HV_FRONT_MAX_POINTS = 2048, 16384
 
 (DKG_OK, DKG_ERR_ARG, DKG_ERR_UNSUPPORTED, DKG_ERR_WORKSPACE, DKG_ERR_HIP, DKG_ERR_NO_LINES,
  DKG_ERR_NOT_PD) = range(7)
@@ -115,6 +117,12 @@ SIGNATURES = {
                               c_uint, c_double, c_double, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "dkg_hvkg_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dkg_hypervolume": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_double), c_void_p, c_void_p, c_void_p]),
+    "dkg_dominated_boxes_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "dkg_dominated_boxes": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_double), c_int, c_void_p, c_void_p,
+                                    c_void_p, c_size_t, c_void_p]),
+    "dkg_hypervolume_front_workspace": (c_size_t, [c_int, c_int, c_int]),
+    "dkg_hypervolume_front": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_double), c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
     "dkg_abi_version": (c_int, []),
     "dkg_last_error": (c_char_p, []),
     "dkg_frag_elems": (c_size_t, [c_int, c_int]),

@@ -145,7 +145,8 @@ def run_mobo(problem: GPProblem, hyper: Dict[str, Sequence[float]], separate: bo
              spec: Optional[DiscreteKgOptimisationSpec] = None, seed: int = 0,
              catalog: Optional[DataCatalog] = None, run_key: Optional[str] = None,
              fit_hyperparams: str = "never", incremental: bool = False,
-             fit_on_device: bool = False, joint_objectives: bool = False, metrics: bool = False) -> Dict[str, List]:
+             fit_on_device: bool = False, joint_objectives: bool = False, metrics: bool = False,
+             metrics_on_device: bool = False) -> Dict[str, List]:
     """``bo_loop.run_mobo`` with the discrete-KG strategy for ``n_iter`` BO steps; returns the
     query history (x, objective index or None for full evaluation, observed values, acquisition).
     With ``catalog`` it also writes the reference's checkpoints and query-history table under
@@ -175,12 +176,17 @@ def run_mobo(problem: GPProblem, hyper: Dict[str, Sequence[float]], separate: bo
     ``save_timings`` at the end (``:558-561``).  The NSGA-II uniforms and the metric's scalarisation weights come
     from generators of their own seeded from ``seed``, the run and the iteration, so a run with metrics makes
     exactly the decisions of the run without.  The reference instead draws the weights' seed from the global RNG
-    (``scalarisations_seed=None``), and pygmo seeds itself.
+    (``scalarisations_seed=None``), and pygmo seeds itself.  ``metrics_on_device`` (off by default; m <= 3): the
+    four hypervolumes of a metrics row come from ``dkg_amd.boxes.hypervolume_front`` on ``problem.device`` instead of
+    the host recursion.  The two routes sum the same non-negative terms in different orders, so the
+    rows agree to rounding, not to the bit; the decisions of the run do not read them.
 
     Where the gradient plans take their rows from follows the module default (``dkg_amd.set_gradient_rows``);
     there is no argument for it here."""
     if metrics and problem.ref_point is None:
         raise ValueError("metrics=True needs problem.ref_point (GPProblem(..., ref_point=...))")
+    if metrics_on_device and torch.device(problem.device).type != "cuda":
+        raise ValueError("metrics_on_device needs a problem on a ROCm device")
     if fit_hyperparams not in ("never", "once", "always"):
         raise ValueError(f"Unexpected value for fit_hyperparams. Got {fit_hyperparams!r}")
     on = incremental and fit_hyperparams != "always"
@@ -188,14 +194,15 @@ def run_mobo(problem: GPProblem, hyper: Dict[str, Sequence[float]], separate: bo
     try:
         return _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations, spec, seed, catalog,
                          run_key, fit_hyperparams, _fit_device(problem, fit_on_device and fit_hyperparams == "always"),
-                         joint_objectives, metrics)
+                         joint_objectives, metrics, problem.device if metrics_on_device else None)
     finally:
         if on:
             set_incremental_state(prev)
 
 
 def _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations, spec, seed, catalog, run_key,
-              fit_hyperparams, fit_device=None, joint_objectives=False, metrics=False) -> Dict[str, List]:
+              fit_hyperparams, fit_device=None, joint_objectives=False, metrics=False,
+              metrics_device=None) -> Dict[str, List]:
     m, d = problem.num_objectives, problem.gp.input_dim
     # the pipeline's --seed (main.py:235, utils.set_random_seed): every later draw comes from the global RNG, as
     # in the reference -- the initial Sobol points (generate_initial_data, bo_loop.py:48-49: no seed), each
@@ -256,7 +263,8 @@ def _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations,
         if catalog is not None:
             catalog.save_posterior_pareto(run_key, iteration, pset, pfront)
         perf = estimate_expected_performance_after_scalarisation(pset, pfront, problem, scalarisations_seed=base + 2)
-        hv = estimate_hypervolume_from_posterior_mean(pset, pfront, problem, problem.ref_point)
+        hv = estimate_hypervolume_from_posterior_mean(pset, pfront, problem, problem.ref_point,
+                                                      device=metrics_device)
         metrics_history.append({**hv, **perf, "cost": float(sum(qh["cost"]))})
         timings_history.append({"iteration": iteration, "bo": bo_time, "fit": fit_time,
                                 "metrics": time.monotonic() - t0})
@@ -322,7 +330,8 @@ def _run_mobo(problem, hyper, separate, n_iter, n_init, costs, n_scalarisations,
 def run_smoke(problem: GPProblem, hyper: Dict[str, Sequence[float]], seed: int = 0,
               catalog: Optional[DataCatalog] = None, fit_hyperparams: str = "never",
               incremental: bool = False, fit_on_device: bool = False,
-              joint_objectives: bool = False, metrics: bool = False) -> Dict[str, Dict]:
+              joint_objectives: bool = False, metrics: bool = False,
+              metrics_on_device: bool = False) -> Dict[str, Dict]:
     """``run_pipeline`` under ``SMOKE_TEST`` (``main.py:171-216``): the separate-evaluation run and
     the full-evaluation run, two BO steps each; with ``catalog`` both write the reference's files.
     ``fit_hyperparams = "once"`` fits the hyperparameters first (``main.py:181-182``, saved to the catalog's
@@ -337,6 +346,7 @@ def run_smoke(problem: GPProblem, hyper: Dict[str, Sequence[float]], seed: int =
     / ``"max_possible_expected_scalarisation"``; a problem without ``ref_point`` gets
     ``calculate_reference_point`` of that front (``gp_testproblem.py:236-247``).  Then both runs record their
     metrics (``run_mobo``).  The seeds are the metrics' own, so both runs make the decisions they make without.
+    ``metrics_on_device``: as ``run_mobo``'s, for both runs.
 
     The gradient-rows mode of both runs is the module default (``dkg_amd.set_gradient_rows``), as in ``run_mobo``."""
     extra = {}
@@ -363,7 +373,7 @@ def run_smoke(problem: GPProblem, hyper: Dict[str, Sequence[float]], seed: int =
             y = torch.zeros(1, dtype=torch.double)
             catalog.save_model_hyperparameters(
                 to_state_dict(surrogate([x] * problem.num_objectives, [y] * problem.num_objectives, hyper), cfg))
-    mk = {"metrics": True} if metrics else {}
+    mk = {"metrics": True, "metrics_on_device": metrics_on_device} if metrics else {}
     return {"separate": run_mobo(problem, hyper, separate=True, seed=seed, catalog=catalog,
                                  fit_hyperparams=fit_hyperparams, incremental=incremental,
                                  fit_on_device=fit_on_device, joint_objectives=joint_objectives, **mk),

@@ -60,7 +60,8 @@ def compute_sample_box_decomposition(pareto_fronts: List[Tensor], maximize: bool
     * Samples with fewer boxes are padded with zero-width boxes ``[0, 0]``, as the reference pads (:243-245).
     * ``maximize=False``: the fronts are negated, decomposed, and the boxes mirrored back.
 
-    m >= 3 raises ``UnsupportedError``: pass your own bounds to the acquisition."""
+    m >= 3 raises ``UnsupportedError``: ``dkg_amd.boxes.dominated_boxes`` builds the boxes of three objectives on
+    the device (and these, bit for bit, for one and two), or pass your own bounds to the acquisition."""
     if len(pareto_fronts) == 0:
         raise ValueError("Expected at least one Pareto front.")
     if not all(pf.dim() == 2 for pf in pareto_fronts):

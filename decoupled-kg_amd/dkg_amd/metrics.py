@@ -102,22 +102,28 @@ def _hv(P: np.ndarray, ref: np.ndarray) -> float:
     return float(hv)
 
 
-def hypervolume(points, ref_point) -> float:
+def hypervolume(points, ref_point, device=None) -> float:
     """The exact hypervolume dominated by ``points`` [n, m] above ``ref_point`` [m]
-    (``DominatedPartitioning(ref_point, points).compute_hypervolume()``)."""
+    (``DominatedPartitioning(ref_point, points).compute_hypervolume()``).  ``device`` (default None: the host
+    recursion below): for m <= 3 the sweep of ``dkg_amd.boxes.hypervolume_front`` on that ROCm device, the same
+    number to rounding; m > 3 stays on the host."""
+    if device is not None and len(ref_point) <= 3:
+        from .boxes import hypervolume_front
+
+        return float(hypervolume_front(torch.as_tensor(points).reshape(-1, len(ref_point)), ref_point, device=device))
     P = np.asarray(torch.as_tensor(points).detach().cpu().numpy(), dtype=np.float64).reshape(-1, len(ref_point))
     ref = np.asarray(torch.as_tensor(ref_point).detach().cpu().numpy(), dtype=np.float64).reshape(-1)
     return _hv(P[(P > ref).all(-1)], ref)
 
 
-def estimate_hypervolume(pareto_front: Tensor, ref_point: Tensor, return_upper: bool = True):
+def estimate_hypervolume(pareto_front: Tensor, ref_point: Tensor, return_upper: bool = True, device=None):
     """Lower and (estimated) upper bounds of the dominated hypervolume from a sample of the front
     (``botorch_hypervolume.py:66-95``): the lower bound is the sample's hypervolume; the upper bound is the box
     between the reference point and the sample's ideal point less the hypervolume of the negated points above
-    the negated ideal point."""
+    the negated ideal point.  ``device``: as ``hypervolume``'s."""
     pareto_front = torch.as_tensor(pareto_front)
     ref_point = torch.as_tensor(ref_point).to(pareto_front)
-    lower = hypervolume(pareto_front, ref_point)
+    lower = hypervolume(pareto_front, ref_point, device=device)
     if not return_upper:
         return lower
     ideal, _ = pareto_front.max(dim=0)
@@ -125,19 +131,19 @@ def estimate_hypervolume(pareto_front: Tensor, ref_point: Tensor, return_upper: 
     if not above.any():
         upper = 0
     else:
-        complement = hypervolume(-pareto_front[above], -ideal)
+        complement = hypervolume(-pareto_front[above], -ideal, device=device)
         upper = torch.prod(ideal - ref_point).item() - complement
     return lower, upper
 
 
 def estimate_hypervolume_from_posterior_mean(pareto_set, pareto_front, true_problem, ref_point, *,
-                                             tkwargs=None) -> Dict[str, float]:
+                                             tkwargs=None, device=None) -> Dict[str, float]:
     """Bounds of the hypervolume of the model's front and of the true image of its Pareto set
-    (``botorch_hypervolume.py:12-42``; same keys)."""
+    (``botorch_hypervolume.py:12-42``; same keys).  ``device``: as ``hypervolume``'s, for all four."""
     pset = _tensor(pareto_set, tkwargs)
     front = _tensor(pareto_front, tkwargs)
     image = torch.as_tensor(true_problem(pset)).to(front)
     ref = torch.as_tensor(ref_point).to(front)
-    pfront_lo, pfront_hi = estimate_hypervolume(front, ref)
-    pset_lo, pset_hi = estimate_hypervolume(image, ref)
+    pfront_lo, pfront_hi = estimate_hypervolume(front, ref, device=device)
+    pset_lo, pset_hi = estimate_hypervolume(image, ref, device=device)
     return {"pfront_hv_lo": pfront_lo, "pfront_hv_hi": pfront_hi, "pset_hv_lo": pset_lo, "pset_hv_hi": pset_hi}

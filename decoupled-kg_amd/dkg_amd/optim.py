@@ -354,8 +354,9 @@ class JesOptimisationSpec:
     (``sample_discrete_pareto_optimal_points``, ``jes_sample_pareto.py``); ``with_device_sampler`` builds a spec whose
     sampler is this library's (``dkg_amd.jes_pareto``).  The sets are
     in the model's input space (the unit cube), the fronts in the untransformed output space; samples may hold
-    different numbers of points.  The boxes come from ``compute_sample_box_decomposition`` (one or two
-    objectives; ``hypercell_bounds_fn(pareto_fronts)`` replaces it for more).
+    different numbers of points.  The boxes come from ``compute_sample_box_decomposition`` on the host for one or
+    two objectives and from ``dkg_amd.boxes.dominated_boxes`` on the spec's device for three;
+    ``hypercell_bounds_fn(pareto_fronts)`` replaces either.
     """
 
     def __init__(self, estimation_type: str, num_pareto_samples: int, num_pareto_points: int, num_restarts: int,
@@ -412,7 +413,13 @@ class JesOptimisationSpec:
         pareto_sets, pareto_fronts = self.pareto_sampler(model, _get_standard_bounds(input_dim),
                                                          num_samples=self.num_pareto_samples,
                                                          target_num_points=self.num_pareto_points)
-        fn = self.hypercell_bounds_fn or compute_sample_box_decomposition
+        fn = self.hypercell_bounds_fn
+        if fn is None:
+            if pareto_fronts[0].shape[-1] >= 3:  # m <= 2 keeps the host function and its bits
+                from .boxes import dominated_boxes
+
+                return pareto_sets, pareto_fronts, dominated_boxes(pareto_fronts, device=self.device)
+            fn = compute_sample_box_decomposition
         return pareto_sets, pareto_fronts, fn(pareto_fronts)
 
     def _acq(self, model, samples, target: Optional[int]):

@@ -42,7 +42,7 @@ extern "C" {
 #define DKG_ABI_VERSION 9  /* 9: dkg_append_observation; 8: dkg_plan_forward_batches, dkg_plan_time_stage_batches */
 /* Added under 9 since (new symbols only; nothing that existed changed): dkg_mll_*, dkg_posterior_mean, dkg_pareto_*,
  * dkg_jes_*, dkg_rff_workspace, dkg_rff_weights, dkg_rff_eval, dkg_debug_rff_gram, dkg_pareto_paths_workspace,
- * dkg_pareto_nsga2_paths, dkg_pareto_prune, dkg_hvkg_*, dkg_hypervolume. */
+ * dkg_pareto_nsga2_paths, dkg_pareto_prune, dkg_hvkg_*, dkg_hypervolume, dkg_dominated_boxes*, dkg_hypervolume_front*. */
 #define DKG_MAX_OUTPUTS 8   /* outputs (objectives) per model list */
 #define DKG_MAX_DIM 16      /* input dimension d */
 
@@ -512,6 +512,56 @@ int dkg_hvkg_forward(const void* host_plan, const double* x_full, int B, double*
  * positive.  DKG_ERR_UNSUPPORTED for m not in {2, 3} or num_pareto beyond the limit. */
 int dkg_hypervolume(const double* Y, int S, int num_pareto, int m, const double* ref_point, double* hv, double* dhv,
                     void* stream);
+
+/* ---- Dominated-space boxes and the hypervolume of large fronts, m <= 3 (dkg_boxes.hip) --------------------------
+ * The region a point set dominates above a reference point, cut into disjoint boxes (what BoTorch's
+ * DominatedPartitioning gives the reference's JES, jes_sample_pareto.py:235-347), and the sum of their volumes (the
+ * hypervolume of the BO metrics, botorch_hypervolume.py).  All objectives are maximised; everything is fp64.
+ * DESIGN.md 8g.  The specification:
+ *   A point qualifies if it is strictly above ref in every objective; other points (NaN and padding rows included)
+ *   contribute nothing.  Boxes are (lo, hi].  Every corner coordinate is a copy of an input value or of ref: no
+ *   arithmetic makes a corner.  Boxes with an empty interior are not emitted.
+ *   m = 1: the one box (ref, max].
+ *   m = 2: the staircase (a_1, b_1) ... (a_k, b_k) of the non-dominated qualifying points (repeated points once), a
+ *     ascending and b descending; box j is (a_{j-1}, a_j] x (ref_1, b_j] with a_0 = ref_0, emitted by ascending j.
+ *   m = 3: take the qualifying points in level order: y_2 descending, then index ascending.  For point p in that
+ *     order let s_1 ... s_t be the 2-d staircase in (y_0, y_1) of the points before it, y_0 ascending: the earlier
+ *     points not weakly dominated in (y_0, y_1) by another earlier point; of equal pairs the first in level order
+ *     stays.  The region only p adds, (ref_0, p_0] x (ref_1, p_1] less what the earlier points dominate, is cut
+ *     into vertical strips: strip i is (s_{i-1,0}, min(s_{i,0}, p_0)] x (s_{i,1}, p_1] with s_{0,0} = ref_0, and
+ *     the last strip is (s_{t,0}, p_0] x (ref_1, p_1].  Each strip with an interior gives the box
+ *     strip x (ref_2, p_2].  Boxes are emitted in level order of p, and within p by ascending strip.
+ *   Count bound: a point emits at most (staircase points it removes + 1) boxes, so K points give at most 2K - 1
+ *     boxes at m = 3, at most K at m = 2 and 1 at m = 1.
+ *   hv = the sum over the boxes of prod(hi - lo); every term is a product of non-negative differences, so nothing
+ *     cancels.
+ * Rounding of dkg_hypervolume_front: |hv - exact| <= (L + 4) 2^-52 exact with L = K + ceil(K / 1024) + 10, the
+ * longest chain of additions a term passes through: a point's strips are summed in its lane in walk order, each by
+ * one fma (at most K strips: K - 1 additions after the first, which adds to zero); the per-point volumes are summed
+ * by 1024 lanes over every 1024th (ceil(K / 1024) - 1 additions after the first) and then by a binary tree (10).
+ * That is K + ceil(K / 1024) + 8; the term itself rounds five times (two differences into the fma, the fma, the
+ * last difference and its product), one of them the first link of the chain and four the "+ 4"; the other 2 of L
+ * cover the second-order terms.  L <= K + 26 <= K + 64.
+ * Samples with fewer points are padded by the caller with rows that do not qualify (ref itself will do).  Results
+ * depend on a sample's qualifying points only: two calls give the same bits, a set's result does not depend on S or
+ * on its row, and appended rows that do not qualify change no bit.  Stream ordered, nothing synchronises, no
+ * atomics, no workgroup waits on another.  Limits (DKG_ERR_UNSUPPORTED beyond them): m <= 3, S <= 65535, K <=
+ * DKG_BOXES_MAX_POINTS for the boxes and DKG_HV_FRONT_MAX_POINTS for the volume, J <= DKG_JES_MAX_BOXES. */
+#define DKG_BOXES_MAX_POINTS 2048      /* 2K - 1 <= DKG_JES_MAX_BOXES */
+#define DKG_HV_FRONT_MAX_POINTS 16384  /* dkg_pareto_rank's cap */
+/* Bytes of device scratch for S sets of K points; 0 for sizes the call refuses. */
+size_t dkg_dominated_boxes_workspace(int S, int K, int m);
+/* bounds[s][0][j] / bounds[s][1][j]: the lower / upper corner of box j < count[s] of set s; rows count[s] ... J - 1
+ * are [0, 0] boxes, as the reference pads.  Y: device [S][K][m]; ref_point: host [m] (JES passes -1e10 everywhere);
+ * bounds: device [S][2][J][m]; count: device [S].  J must hold the count bound (1 / K / 2K - 1 at m = 1 / 2 / 3).
+ * Two launches.  DKG_ERR_ARG for NULL pointers, sizes < 1 or J below the count bound; DKG_ERR_UNSUPPORTED beyond the
+ * limits; DKG_ERR_WORKSPACE for a short workspace; all checked before any HIP call. */
+int dkg_dominated_boxes(const double* Y, int S, int K, int m, const double* ref_point, int J, double* bounds,
+                        int* count, void* work, size_t work_bytes, void* stream);
+size_t dkg_hypervolume_front_workspace(int S, int K, int m);
+/* hv[s] (device [S]) = the hypervolume of set s above ref_point.  Three launches.  Errors as above. */
+int dkg_hypervolume_front(const double* Y, int S, int K, int m, const double* ref_point, double* hv, void* work,
+                          size_t work_bytes, void* stream);
 
 /* Bytes of scratch dkg_forward needs for (m outputs, N points, B candidates, S weights). */
 size_t dkg_forward_workspace(const dkg_output* outs, int m, int N, int B, int S);
