@@ -29,6 +29,7 @@
 // depends on the sample's qualifying points only.
 #include <cmath>
 
+#include "dkg_acq.h"
 #include "dkg_stages.h"
 
 namespace dkg {
@@ -47,14 +48,15 @@ struct BoxWs {
 BoxWs box_ws(int S, int K) {
   BoxWs w;
   const size_t n = (size_t)S * K;
-  w.sx = 0;
-  w.sy = w.sx + n * sizeof(double);
-  w.sz = w.sy + n * sizeof(double);
-  w.hvp = w.sz + n * sizeof(double);
-  w.slvl = w.hvp + n * sizeof(double);
-  w.lrank = w.slvl + n * sizeof(int);
-  w.nq = w.lrank + n * sizeof(int);
-  w.total = (w.nq + (size_t)S * sizeof(int) + 255) & ~(size_t)255;
+  Carve c;  // the sections follow each other as they are; the end is rounded to 256
+  w.sx = c.take(n * sizeof(double), 1);
+  w.sy = c.take(n * sizeof(double), 1);
+  w.sz = c.take(n * sizeof(double), 1);
+  w.hvp = c.take(n * sizeof(double), 1);
+  w.slvl = c.take(n * sizeof(int), 1);
+  w.lrank = c.take(n * sizeof(int), 1);
+  w.nq = c.take((size_t)S * sizeof(int));
+  w.total = c.total();
   return w;
 }
 
@@ -288,7 +290,6 @@ bool box_sizes_ok(int S, int K, int m, int k_max) {
 
 BoxArgs box_args(const double* Y, int S, int K, int m, const double* ref, void* work) {
   const BoxWs w = box_ws(S, K);
-  char* base = static_cast<char*>(work);
   BoxArgs a{};
   a.Y = Y;
   a.K = K;
@@ -296,13 +297,13 @@ BoxArgs box_args(const double* Y, int S, int K, int m, const double* ref, void* 
   a.rx = ref[0];
   a.ry = m == 3 ? ref[1] : 0.0;
   a.rz = m == 3 ? ref[2] : (m == 2 ? ref[1] : 0.0);
-  a.sx = reinterpret_cast<double*>(base + w.sx);
-  a.sy = reinterpret_cast<double*>(base + w.sy);
-  a.sz = reinterpret_cast<double*>(base + w.sz);
-  a.hvp = reinterpret_cast<double*>(base + w.hvp);
-  a.slvl = reinterpret_cast<int*>(base + w.slvl);
-  a.lrank = reinterpret_cast<int*>(base + w.lrank);
-  a.nq = reinterpret_cast<int*>(base + w.nq);
+  a.sx = at<double>(work, w.sx);
+  a.sy = at<double>(work, w.sy);
+  a.sz = at<double>(work, w.sz);
+  a.hvp = at<double>(work, w.hvp);
+  a.slvl = at<int>(work, w.slvl);
+  a.lrank = at<int>(work, w.lrank);
+  a.nq = at<int>(work, w.nq);
   return a;
 }
 

@@ -23,8 +23,10 @@
 // No atomics; every sum runs in a fixed order that depends on the restart's own data only, so two calls give the
 // same bits and a restart's results do not depend on B or on its row.
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 
+#include "dkg_acq.h"
 #include "dkg_stages.h"
 
 namespace dkg {
@@ -57,17 +59,6 @@ struct HvkgHost {
   dkg_output tab[HK_MAXM];
   double z[DKG_HVKG_MAX_FANTASIES * HK_MAXM];
 };
-
-// f(integral_constant<int, KIND>) for the covariance family `kind` (wave-uniform)
-template <class F>
-__device__ __forceinline__ void with_kind(int kind, F&& f) {
-  switch (kind) {
-    case DKG_MATERN12: f(std::integral_constant<int, DKG_MATERN12>{}); break;
-    case DKG_MATERN32: f(std::integral_constant<int, DKG_MATERN32>{}); break;
-    case DKG_RBF: f(std::integral_constant<int, DKG_RBF>{}); break;
-    default: f(std::integral_constant<int, DKG_MATERN52>{}); break;
-  }
-}
 
 // The sum of one value per thread over the workgroup, returned to every thread: wave_sum, then the waves in index
 // order.  red: LDS [HK_WAVES].  Two barriers; every thread of the workgroup calls it.
@@ -162,8 +153,7 @@ __global__ __launch_bounds__(HK_WAVES* WAVE) void hvkg_cand_kernel(HvkgCandArgs 
     for (int j = tid; j < np; j += HK_WAVES * WAVE) {
       const int jc = min(j, n - 1);
       double xs[DM];
-#pragma unroll
-      for (int k = 0; k < DM; ++k) xs[k] = tx[(size_t)jc * d + min(k, d - 1)] * il[k];
+      scaled_point<DM>(xs, tx + (size_t)jc * d, il, d);
       const double v = cross_kernel_term<DM, KIND>(xr, xs, d, os, tab);
       kv[j] = (j < n) ? v : 0.0;
     }
@@ -214,15 +204,13 @@ __global__ __launch_bounds__(HK_WAVES* WAVE) void hvkg_fantasy_kernel(HvkgFanArg
   const int off = a.rows - a.R;             // 1 with a candidate row, 0 in value-function mode
   const double* __restrict__ xb = a.x + (size_t)b * a.rows * d;
   double il[DM];
-#pragma unroll
-  for (int k = 0; k < DM; ++k) il[k] = o.inv_lengthscale[min(k, d - 1)];
+  clamped_row<DM>(il, o.inv_lengthscale, d);
   for (int pq = wave; pq < HK_POINTS; pq += HK_WAVES) {
     const int r = blockIdx.x * HK_POINTS + pq;
     if (r >= a.R) break;  // wave-uniform
     const double coef = obs ? a.z[(size_t)(r / a.Np) * a.m + i] / sig : 0.0;
     double xr[DM];
-#pragma unroll
-    for (int k = 0; k < DM; ++k) xr[k] = xb[(size_t)(off + r) * d + min(k, d - 1)] * il[k];
+    scaled_point<DM>(xr, xb + (size_t)(off + r) * d, il, d);
     double macc = 0.0, cacc = 0.0, ga[DM];
 #pragma unroll
     for (int k = 0; k < DM; ++k) ga[k] = 0.0;
@@ -239,30 +227,19 @@ __global__ __launch_bounds__(HK_WAVES* WAVE) void hvkg_fantasy_kernel(HvkgFanArg
         macc = fma(kv, als[jc], macc);
         cacc = fma(kv, ws[jc], cacc);
         if (a.grad) {
-          double r2 = 0.0;
-#pragma unroll
-          for (int k = 0; k < DM; ++k) {
-            const double t = xr[k] - xj[min(k, d - 1)];
-            r2 = fma(t, (k < d) ? t : 0.0, r2);
-          }
+          double xjr[DM];
+          clamped_row<DM>(xjr, xj, d);
           const double aj = obs ? fma(-coef, ws[jc], als[jc]) : als[jc];
-          const double h = (j < n) ? os * kernel_dprofile_t<KIND>(r2) * aj : 0.0;
+          const double h = (j < n) ? os * kernel_dprofile_t<KIND>(sq_dist<DM>(xr, xjr, d)) * aj : 0.0;
 #pragma unroll
-          for (int k = 0; k < DM; ++k) ga[k] = fma(h, (xr[k] - xj[min(k, d - 1)]) * il[k], ga[k]);
+          for (int k = 0; k < DM; ++k) ga[k] = fma(h, (xr[k] - xjr[k]) * il[k], ga[k]);
         }
       }
       if (obs) {
         double xc[DM];
-#pragma unroll
-        for (int k = 0; k < DM; ++k) xc[k] = xb[min(k, d - 1)] * il[k];
+        scaled_point<DM>(xc, xb, il, d);
         kxx = cross_kernel_term<DM, KIND>(xr, xc, d, os, tab);
-        double r2 = 0.0;
-#pragma unroll
-        for (int k = 0; k < DM; ++k) {
-          const double t = xr[k] - xc[k];
-          r2 = fma(t, (k < d) ? t : 0.0, r2);
-        }
-        hxx = os * kernel_dprofile_t<KIND>(r2);
+        hxx = os * kernel_dprofile_t<KIND>(sq_dist<DM>(xr, xc, d));
       }
     });
     const double mu = o.mean_constant + wave_sum(macc);
@@ -486,11 +463,8 @@ __global__ __launch_bounds__(HK_WAVES* WAVE) void hvkg_finish_kernel(HvkgFinArgs
     }
     const double C = block_sum(cp, red);
     double il[DM], xc[DM];
-#pragma unroll
-    for (int k = 0; k < DM; ++k) {
-      il[k] = o.inv_lengthscale[min(k, d - 1)];
-      xc[k] = xb[min(k, d - 1)] * il[k];
-    }
+    clamped_row<DM>(il, o.inv_lengthscale, d);
+    scaled_point<DM>(xc, xb, il, d);
     // t_j = sum_r a_r s kappa(X_j, x'_r), the fantasy points in order (a point with a_r = 0 adds nothing)
     with_kind(o.kernel, [&](auto kind_c) {
       constexpr int KIND = decltype(kind_c)::value;
@@ -498,15 +472,13 @@ __global__ __launch_bounds__(HK_WAVES* WAVE) void hvkg_finish_kernel(HvkgFinArgs
       for (int j = tid; j < np; j += HK_WAVES * WAVE) {
         const int jc = min(j, n - 1);
         double xs[DM];
-#pragma unroll
-        for (int k = 0; k < DM; ++k) xs[k] = tx[(size_t)jc * d + min(k, d - 1)] * il[k];
+        scaled_point<DM>(xs, tx + (size_t)jc * d, il, d);
         double t = 0.0;
         for (int r = 0; r < R; ++r) {
           const double ar = av[r];
           if (ar == 0.0) continue;  // uniform
           double xr[DM];
-#pragma unroll
-          for (int k = 0; k < DM; ++k) xr[k] = xb[(size_t)(off + r) * d + min(k, d - 1)] * il[k];
+          scaled_point<DM>(xr, xb + (size_t)(off + r) * d, il, d);
           t = fma(ar, cross_kernel_term<DM, KIND>(xr, xs, d, os, tab), t);
         }
         tv[j] = (j < n) ? t : 0.0;
@@ -526,16 +498,12 @@ __global__ __launch_bounds__(HK_WAVES* WAVE) void hvkg_finish_kernel(HvkgFinArgs
     with_kind(o.kernel, [&](auto kind_c) {
       constexpr int KIND = decltype(kind_c)::value;
       for (int j = tid; j < n; j += HK_WAVES * WAVE) {
-        double df[DM], r2 = 0.0;
-#pragma unroll
-        for (int k = 0; k < DM; ++k) {
-          df[k] = xc[k] - tx[(size_t)j * d + min(k, d - 1)] * il[k];
-          r2 = fma(df[k], (k < d) ? df[k] : 0.0, r2);
-        }
+        double xs[DM];
+        scaled_point<DM>(xs, tx + (size_t)j * d, il, d);
         const double vj = fma(c3, wv[j], -uv[j] * is);
-        const double h = os * kernel_dprofile_t<KIND>(r2) * vj;
+        const double h = os * kernel_dprofile_t<KIND>(sq_dist<DM>(xc, xs, d)) * vj;
 #pragma unroll
-        for (int k = 0; k < DM; ++k) pg[k] = fma(h, df[k] * il[k], pg[k]);
+        for (int k = 0; k < DM; ++k) pg[k] = fma(h, (xc[k] - xs[k]) * il[k], pg[k]);
       }
     });
 #pragma unroll
@@ -566,22 +534,18 @@ struct HvkgWs {
 HvkgWs hvkg_ws(int m, int d, int Nf, int Np, int max_B) {
   const size_t B = (size_t)max_B, R = (size_t)Nf * Np, D = sizeof(double);
   HvkgWs w{};
-  size_t off = 0;
-  auto carve = [&](size_t& at, size_t bytes) {
-    at = off;
-    off = up256(off + bytes);
-  };
-  carve(w.tab, (size_t)m * sizeof(dkg_output));
-  carve(w.z, (size_t)Nf * m * D);
-  carve(w.w, B * m * HK_WSTRIDE * D);
-  carve(w.sig, B * m * D);
-  carve(w.Y, B * R * m * D);
-  carve(w.cxx, B * R * m * D);
-  carve(w.dY, B * R * m * d * D);
-  carve(w.dkx, B * R * m * d * D);
-  carve(w.hv, B * Nf * D);
-  carve(w.dhv, B * R * m * D);
-  w.total = off;
+  Carve c;
+  w.tab = c.take((size_t)m * sizeof(dkg_output));
+  w.z = c.take((size_t)Nf * m * D);
+  w.w = c.take(B * m * HK_WSTRIDE * D);
+  w.sig = c.take(B * m * D);
+  w.Y = c.take(B * R * m * D);
+  w.cxx = c.take(B * R * m * D);
+  w.dY = c.take(B * R * m * d * D);
+  w.dkx = c.take(B * R * m * d * D);
+  w.hv = c.take(B * Nf * D);
+  w.dhv = c.take(B * R * m * D);
+  w.total = c.total();
   return w;
 }
 
@@ -598,7 +562,7 @@ int hvkg_check_sizes(int m, int d, int Nf, int Np, int max_B) {
     return failf(DKG_ERR_ARG, "m=%d d=%d num_fantasies=%d num_pareto=%d max_B=%d", m, d, Nf, Np, max_B);
   int st = hv_check_m(m);
   if (st) return st;
-  if (d > DKG_MAX_DIM) return failf(DKG_ERR_UNSUPPORTED, "d=%d (supported 1..%d)", d, DKG_MAX_DIM);
+  if ((st = check_dims(m, d))) return st;
   if (Nf > DKG_HVKG_MAX_FANTASIES)
     return failf(DKG_ERR_UNSUPPORTED, "num_fantasies=%d (supported <= %d)", Nf, DKG_HVKG_MAX_FANTASIES);
   if (Np > DKG_HVKG_MAX_PARETO)
@@ -607,21 +571,6 @@ int hvkg_check_sizes(int m, int d, int Nf, int Np, int max_B) {
     return failf(DKG_ERR_UNSUPPORTED, "max_B=%d restarts (supported <= %d)", max_B, DKG_HVKG_MAX_RESTARTS);
   return DKG_OK;
 }
-
-template <class K, class A>
-void hvkg_launch(K kern, dim3 grid, size_t lds, hipStream_t s, const A& a) {
-  raise_lds_limit(reinterpret_cast<const void*>(kern), lds);
-  hipLaunchKernelGGL(kern, grid, dim3(HK_WAVES * WAVE), lds, s, a);
-}
-
-// kern<2|4|8|16> by the dimension bucket
-#define HVKG_BY_DIM(d, kern, ...)                         \
-  switch (dim_bucket(d)) {                                \
-    case 2: hvkg_launch(kern<2>, __VA_ARGS__); break;     \
-    case 4: hvkg_launch(kern<4>, __VA_ARGS__); break;     \
-    case 8: hvkg_launch(kern<8>, __VA_ARGS__); break;     \
-    default: hvkg_launch(kern<16>, __VA_ARGS__); break;   \
-  }
 
 int launch_hv(const double* Y, int S, int Np, int m, const double* ref, double* hv, double* dhv, hipStream_t s) {
   HvkgHvArgs ha{Y, hv, dhv, {0.0, 0.0, 0.0}, Np, m};
@@ -656,13 +605,10 @@ int dkg_hvkg_init(const dkg_output* outs, int m, int d, const double* ref_point,
   if (!std::isfinite(current_value)) return failf(DKG_ERR_ARG, "current_value=%g", current_value);
   int np_max = 16;
   for (int k = 0; k < m; ++k) {
-    const dkg_output& o = outs[k];
-    if (o.n < 1) return failf(DKG_ERR_ARG, "output %d: n=%d training points", k, o.n);
-    if (o.n > 1024) return failf(DKG_ERR_UNSUPPORTED, "output %d: n=%d > 1024 training points", k, o.n);
-    if (o.kernel < DKG_MATERN12 || o.kernel > DKG_RBF) return failf(DKG_ERR_ARG, "output %d: kernel id %d", k, o.kernel);
-    if (!o.inv_lengthscale || !o.train_x || !o.alpha || !o.root_frag)
-      return failf(DKG_ERR_ARG, "output %d: NULL pointer", k);
-    np_max = std::max(np_max, pad16(o.n));
+    char who[32];
+    std::snprintf(who, sizeof who, "output %d", k);
+    if ((st = check_output_state(outs[k], true, who))) return st;
+    np_max = std::max(np_max, pad16(outs[k].n));
   }
   const HvkgWs w = hvkg_ws(m, d, Nf, Np, max_B);
   if (workspace_bytes < w.total)
@@ -671,27 +617,28 @@ int dkg_hvkg_init(const dkg_output* outs, int m, int d, const double* ref_point,
   std::memset(h, 0, sizeof(HvkgHost));
   std::memcpy(h->tab, outs, (size_t)m * sizeof(dkg_output));
   if (mask != 0) std::memcpy(h->z, base_samples, (size_t)Nf * m * sizeof(double));
-  char* base = static_cast<char*>(workspace);
   HvkgPlan& p = h->plan;
   p.m = m; p.d = d; p.Nf = Nf; p.Np = Np; p.R = Nf * Np; p.rows = p.R + (mask != 0 ? 1 : 0);
   p.mask = (int)mask; p.max_B = max_B; p.np_max = np_max;
   for (int i = 0; i < m; ++i) p.ref[i] = ref_point[i];
   p.current = current_value; p.cost = cost;
-  p.tab = reinterpret_cast<const dkg_output*>(base + w.tab);
-  p.z = reinterpret_cast<const double*>(base + w.z);
-  p.w = reinterpret_cast<double*>(base + w.w);
-  p.sig = reinterpret_cast<double*>(base + w.sig);
-  p.Y = reinterpret_cast<double*>(base + w.Y);
-  p.cxx = reinterpret_cast<double*>(base + w.cxx);
-  p.dY = reinterpret_cast<double*>(base + w.dY);
-  p.dkx = reinterpret_cast<double*>(base + w.dkx);
-  p.hv = reinterpret_cast<double*>(base + w.hv);
-  p.dhv = reinterpret_cast<double*>(base + w.dhv);
+  p.tab = at<const dkg_output>(workspace, w.tab);
+  p.z = at<const double>(workspace, w.z);
+  p.w = at<double>(workspace, w.w);
+  p.sig = at<double>(workspace, w.sig);
+  p.Y = at<double>(workspace, w.Y);
+  p.cxx = at<double>(workspace, w.cxx);
+  p.dY = at<double>(workspace, w.dY);
+  p.dkx = at<double>(workspace, w.dkx);
+  p.hv = at<double>(workspace, w.hv);
+  p.dhv = at<double>(workspace, w.dhv);
   hipStream_t s = (hipStream_t)stream;
-  st = hip_status(hipMemcpyAsync(base + w.tab, h->tab, (size_t)m * sizeof(dkg_output), hipMemcpyHostToDevice, s),
+  st = hip_status(hipMemcpyAsync(at<char>(workspace, w.tab), h->tab, (size_t)m * sizeof(dkg_output),
+                                 hipMemcpyHostToDevice, s),
                   "dkg_hvkg_init: table upload");
   if (st) return st;
-  st = hip_status(hipMemcpyAsync(base + w.z, h->z, (size_t)Nf * m * sizeof(double), hipMemcpyHostToDevice, s),
+  st = hip_status(hipMemcpyAsync(at<char>(workspace, w.z), h->z, (size_t)Nf * m * sizeof(double),
+                                 hipMemcpyHostToDevice, s),
                   "dkg_hvkg_init: base samples upload");
   if (st) return st;
   p.magic = HVKG_MAGIC;
@@ -708,25 +655,30 @@ int dkg_hvkg_forward(const void* host_plan, const double* x_full, int B, double*
   hipStream_t s = (hipStream_t)stream;
   const int grad = dacq_dx != nullptr;
   const int npw = p.np_max;
+  const dim3 block(HK_WAVES * WAVE);
   int st;
   if (p.mask != 0) {
     HvkgCandArgs ca{p.tab, x_full, p.w, p.sig, p.m, p.d, p.rows, p.mask};
     const size_t lds = (2 * (size_t)npw + HK_WAVES) * sizeof(double);
-    HVKG_BY_DIM(p.d, hvkg_cand_kernel, dim3(B, p.m), lds, s, ca);
+    by_dim(p.d, [&](auto dm) { launch_lds(hvkg_cand_kernel<decltype(dm)::value>, dim3(B, p.m), block, lds, s, ca); });
     st = hip_status(hipGetLastError(), "hvkg_cand_kernel");
     if (st) return st;
   }
   HvkgFanArgs fa{p.tab, x_full, p.z, p.w, p.sig, p.Y, p.cxx, p.dY, p.dkx, y_out,
                  p.m, p.d, p.R, p.Np, p.rows, p.mask, grad};
-  HVKG_BY_DIM(p.d, hvkg_fantasy_kernel, dim3((p.R + HK_POINTS - 1) / HK_POINTS, p.m, B),
-              hvkg_fan_lds_bytes(npw, p.d), s, fa);
+  by_dim(p.d, [&](auto dm) {
+    launch_lds(hvkg_fantasy_kernel<decltype(dm)::value>, dim3((p.R + HK_POINTS - 1) / HK_POINTS, p.m, B), block,
+               hvkg_fan_lds_bytes(npw, p.d), s, fa);
+  });
   st = hip_status(hipGetLastError(), "hvkg_fantasy_kernel");
   if (st) return st;
   st = launch_hv(p.Y, B * p.Nf, p.Np, p.m, p.ref, p.hv, grad ? p.dhv : nullptr, s);
   if (st) return st;
   HvkgFinArgs xa{p.tab, x_full, p.z, p.w, p.sig, p.cxx, p.dY, p.dkx, p.hv, p.dhv, acq, dacq_dx,
                  p.current, p.cost, p.m, p.d, p.Nf, p.Np, p.R, p.rows, p.mask, npw};
-  HVKG_BY_DIM(p.d, hvkg_finish_kernel, dim3(B), hvkg_fin_lds_bytes(p.R, npw), s, xa);
+  by_dim(p.d, [&](auto dm) {
+    launch_lds(hvkg_finish_kernel<decltype(dm)::value>, dim3(B), block, hvkg_fin_lds_bytes(p.R, npw), s, xa);
+  });
   return hip_status(hipGetLastError(), "hvkg_finish_kernel");
 }
 

@@ -24,8 +24,10 @@
 //                        chain rule to dx ends here with the moments stage's dmu/dx and dvar/dx.  The states
 //                        meet in LDS and are summed in index order.  No atomics anywhere: two calls give the
 //                        same bits, and a candidate's result does not depend on B or on its row.
+#include <cstdio>
 #include <cstring>
 
+#include "dkg_acq.h"
 #include "dkg_stages.h"
 
 namespace dkg {
@@ -77,12 +79,8 @@ __global__ __launch_bounds__(JM_WAVES* WAVE) void jes_moments_kernel(JesMomArgs 
   const int row = blockIdx.x * 16 + (lane & 15);
   const int rowc = min(row, a.B - 1);  // rows past B repeat the last candidate and are never stored
   double xr[DM], il[DM];
-#pragma unroll
-  for (int k = 0; k < DM; ++k) {
-    const int kk = min(k, d - 1);
-    il[k] = o.inv_lengthscale[kk];
-    xr[k] = a.x[(size_t)rowc * d + kk] * il[k];
-  }
+  clamped_row<DM>(il, o.inv_lengthscale, d);
+  scaled_point<DM>(xr, a.x + (size_t)rowc * d, il, d);
   const double os = o.outputscale;
   const double* __restrict__ tx = o.train_x;
   const double* __restrict__ alpha = o.alpha;
@@ -105,7 +103,7 @@ __global__ __launch_bounds__(JM_WAVES* WAVE) void jes_moments_kernel(JesMomArgs 
     }
     // ---- the slab, and the lane's share of the alpha product
     double mpart = 0.0;
-    auto fill = [&](auto kind_c) {
+    with_kind(o.kernel, [&](auto kind_c) {
       constexpr int KIND = decltype(kind_c)::value;
       const const_dptr tab = psi_tab();
       for (int it = 0; it < iters; ++it) {
@@ -113,32 +111,21 @@ __global__ __launch_bounds__(JM_WAVES* WAVE) void jes_moments_kernel(JesMomArgs 
         const int col = 4 * kb + (lane >> 4);
         const int cc = min(col, n - 1);
         double xs[DM];
-#pragma unroll
-        for (int k = 0; k < DM; ++k) xs[k] = tx[(size_t)cc * d + min(k, d - 1)] * il[k];
+        scaled_point<DM>(xs, tx + (size_t)cc * d, il, d);
         double kv;
         if (ch == 0) {
           kv = cross_kernel_term<DM, KIND>(xr, xs, d, os, tab);
         } else {
-          double r2 = 0.0, xsg = 0.0;
+          double xsg = 0.0;
 #pragma unroll
-          for (int k = 0; k < DM; ++k) {
-            const double t = xr[k] - xs[k];
-            r2 = fma(t, (k < d) ? t : 0.0, r2);
-            xsg = (k == g) ? xs[k] : xsg;
-          }
-          kv = os * kernel_dprofile_t<KIND>(r2) * (xg - xsg) * ilg;
+          for (int k = 0; k < DM; ++k) xsg = (k == g) ? xs[k] : xsg;
+          kv = os * kernel_dprofile_t<KIND>(sq_dist<DM>(xr, xs, d)) * (xg - xsg) * ilg;
         }
         const double v = (col < n) ? kv : 0.0;
         mpart = fma(v, alpha[cc], mpart);
         if (kb < KB) slab[kb * 64 + lane] = v;
       }
-    };
-    switch (o.kernel) {
-      case DKG_MATERN12: fill(std::integral_constant<int, DKG_MATERN12>{}); break;
-      case DKG_MATERN32: fill(std::integral_constant<int, DKG_MATERN32>{}); break;
-      case DKG_RBF: fill(std::integral_constant<int, DKG_RBF>{}); break;
-      default: fill(std::integral_constant<int, DKG_MATERN52>{}); break;
-    }
+    });
     __syncthreads();
 
     // ---- D = R^T K^T per column tile: lane l, register r holds Q[l & 15][16 tj + (l >> 4) + 4 r]
@@ -554,18 +541,13 @@ struct JesWs {
 JesWs jes_ws(int m, int P, int d, int max_B) {
   const size_t SO = (size_t)(P + 1) * m, bpad = pad16(max_B);
   JesWs w{};
-  size_t off = 0;
-  w.tab = off;
-  off = up256(off + SO * sizeof(dkg_output));
-  w.mu = off;
-  off = up256(off + SO * bpad * sizeof(double));
-  w.q2 = off;
-  off = up256(off + SO * bpad * sizeof(double));
-  w.dmu = off;
-  off = up256(off + SO * d * bpad * sizeof(double));
-  w.dvar = off;
-  off = up256(off + SO * d * bpad * sizeof(double));
-  w.total = off;
+  Carve c;
+  w.tab = c.take(SO * sizeof(dkg_output));
+  w.mu = c.take(SO * bpad * sizeof(double));
+  w.q2 = c.take(SO * bpad * sizeof(double));
+  w.dmu = c.take(SO * d * bpad * sizeof(double));
+  w.dvar = c.take(SO * d * bpad * sizeof(double));
+  w.total = c.total();
   return w;
 }
 
@@ -573,20 +555,14 @@ JesWs jes_ws(int m, int P, int d, int max_B) {
 int check_sizes(int m, int P, int d, int J, int max_B) {
   if (m < 1 || P < 1 || d < 1 || J < 1 || max_B < 1)
     return failf(DKG_ERR_ARG, "m=%d P=%d d=%d J=%d max_B=%d", m, P, d, J, max_B);
-  if (m > DKG_MAX_OUTPUTS) return failf(DKG_ERR_UNSUPPORTED, "m=%d outputs (supported <= %d)", m, DKG_MAX_OUTPUTS);
-  if (d > DKG_MAX_DIM) return failf(DKG_ERR_UNSUPPORTED, "d=%d (supported 1..%d)", d, DKG_MAX_DIM);
+  const int st = check_dims(m, d);
+  if (st) return st;
   if (P > DKG_JES_MAX_SAMPLES)
     return failf(DKG_ERR_UNSUPPORTED, "P=%d Pareto samples (supported <= %d)", P, DKG_JES_MAX_SAMPLES);
   if (J > DKG_JES_MAX_BOXES) return failf(DKG_ERR_UNSUPPORTED, "J=%d boxes (supported <= %d)", J, DKG_JES_MAX_BOXES);
   if (max_B > DKG_JES_MAX_CANDIDATES)
     return failf(DKG_ERR_UNSUPPORTED, "max_B=%d candidates (supported <= %d)", max_B, DKG_JES_MAX_CANDIDATES);
   return DKG_OK;
-}
-
-template <class K>
-void launch_lds(K kern, dim3 grid, dim3 block, size_t lds, hipStream_t s, const JesMomArgs& a) {
-  raise_lds_limit(reinterpret_cast<const void*>(kern), lds);
-  hipLaunchKernelGGL(kern, grid, block, lds, s, a);
 }
 
 }  // namespace
@@ -609,15 +585,10 @@ int dkg_jes_init(const dkg_output* states, int m, int P, int d, const double* bo
   const int SO = (P + 1) * m;
   int max_np = 16;
   for (int k = 0; k < SO; ++k) {
-    const dkg_output& o = states[k];
-    if (o.n < 1) return failf(DKG_ERR_ARG, "state %d output %d: n=%d training points", k / m, k % m, o.n);
-    if (o.n > 1024)
-      return failf(DKG_ERR_UNSUPPORTED, "state %d output %d: n=%d > 1024 training points", k / m, k % m, o.n);
-    if (o.kernel < DKG_MATERN12 || o.kernel > DKG_RBF)
-      return failf(DKG_ERR_ARG, "state %d output %d: kernel id %d", k / m, k % m, o.kernel);
-    if (!o.inv_lengthscale || !o.train_x || !o.alpha || !o.root_frag)
-      return failf(DKG_ERR_ARG, "state %d output %d: NULL pointer", k / m, k % m);
-    max_np = std::max(max_np, pad16(o.n));
+    char who[48];
+    std::snprintf(who, sizeof who, "state %d output %d", k / m, k % m);
+    if ((st = check_output_state(states[k], true, who))) return st;
+    max_np = std::max(max_np, pad16(states[k].n));
   }
   const JesWs w = jes_ws(m, P, d, max_B);
   if (workspace_bytes < w.total)
@@ -625,18 +596,18 @@ int dkg_jes_init(const dkg_output* states, int m, int P, int d, const double* bo
   JesHost* h = static_cast<JesHost*>(host_plan);
   std::memset(h, 0, sizeof(JesHost));
   std::memcpy(h->tab, states, (size_t)SO * sizeof(dkg_output));
-  char* base = static_cast<char*>(workspace);
   JesPlan& p = h->plan;
   p.m = m; p.P = P; p.d = d; p.J = J; p.target = target; p.only_diag = only_diagonal ? 1 : 0;
   p.max_B = max_B; p.bpad = pad16(max_B); p.SO = SO; p.max_np = max_np;
-  p.tab = reinterpret_cast<const dkg_output*>(base + w.tab);
+  p.tab = at<const dkg_output>(workspace, w.tab);
   p.bounds = bounds;
-  p.mu = reinterpret_cast<double*>(base + w.mu);
-  p.q2 = reinterpret_cast<double*>(base + w.q2);
-  p.dmu = reinterpret_cast<double*>(base + w.dmu);
-  p.dvar = reinterpret_cast<double*>(base + w.dvar);
-  st = hip_status(hipMemcpyAsync(base + w.tab, h->tab, (size_t)SO * sizeof(dkg_output), hipMemcpyHostToDevice,
-                           (hipStream_t)stream), "dkg_jes_init: table upload");
+  p.mu = at<double>(workspace, w.mu);
+  p.q2 = at<double>(workspace, w.q2);
+  p.dmu = at<double>(workspace, w.dmu);
+  p.dvar = at<double>(workspace, w.dvar);
+  st = hip_status(hipMemcpyAsync(at<char>(workspace, w.tab), h->tab, (size_t)SO * sizeof(dkg_output),
+                                 hipMemcpyHostToDevice, (hipStream_t)stream),
+                  "dkg_jes_init: table upload");
   if (st) return st;
   p.magic = JES_MAGIC;
   return DKG_OK;
@@ -653,12 +624,7 @@ int dkg_jes_forward(const void* host_plan, const double* x, int B, double* acq, 
   JesMomArgs ma{p.tab, x, p.mu, p.q2, p.dmu, p.dvar, B, p.d, p.bpad, grad};
   const dim3 mgrid((B + 15) / 16, p.SO), mblock(JM_WAVES * WAVE);
   const size_t mlds = jes_mom_lds_bytes(p.max_np);
-  switch (dim_bucket(p.d)) {
-    case 2: launch_lds(jes_moments_kernel<2>, mgrid, mblock, mlds, s, ma); break;
-    case 4: launch_lds(jes_moments_kernel<4>, mgrid, mblock, mlds, s, ma); break;
-    case 8: launch_lds(jes_moments_kernel<8>, mgrid, mblock, mlds, s, ma); break;
-    default: launch_lds(jes_moments_kernel<16>, mgrid, mblock, mlds, s, ma); break;
-  }
+  by_dim(p.d, [&](auto dm) { launch_lds(jes_moments_kernel<decltype(dm)::value>, mgrid, mblock, mlds, s, ma); });
   int st = hip_status(hipGetLastError(), "jes_moments_kernel");
   if (st) return st;
   JesEntArgs ea{p.tab, p.bounds, p.mu, p.q2, p.dmu, p.dvar, acq, dacq_dx, moments_out,

@@ -31,7 +31,9 @@
 // (crowding) or nearly so (variation).
 #include <algorithm>
 #include <atomic>
+#include <cstdio>
 
+#include "dkg_acq.h"
 #include "dkg_stages.h"
 
 namespace dkg {
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(PM_WAVES* WAVE) void posterior_mean_kernel(MeanArgs
       xr[k] = (a.lb ? unit_cube(xv, a.lb[kk], a.ub[kk]) : xv) * o.inv_lengthscale[kk];
     }
     double acc = 0.0;
-    auto chain = [&](auto kind_c) {
+    with_kind(o.kernel, [&](auto kind_c) {
       constexpr int KIND = decltype(kind_c)::value;
       const const_dptr tab = psi_tab();
       for (int it = 0; it < iters; ++it) {
@@ -83,13 +85,7 @@ __global__ __launch_bounds__(PM_WAVES* WAVE) void posterior_mean_kernel(MeanArgs
         const double kv = cross_kernel_term<DM, KIND>(xr, xs + (size_t)jc * d, d, os, tab);
         acc = fma((j < n) ? kv : 0.0, als[jc], acc);
       }
-    };
-    switch (o.kernel) {
-      case DKG_MATERN12: chain(std::integral_constant<int, DKG_MATERN12>{}); break;
-      case DKG_MATERN32: chain(std::integral_constant<int, DKG_MATERN32>{}); break;
-      case DKG_RBF: chain(std::integral_constant<int, DKG_RBF>{}); break;
-      default: chain(std::integral_constant<int, DKG_MATERN52>{}); break;
-    }
+    });
     const double s = wave_sum(acc);
     if (lane == 0) a.mean[(size_t)p * a.m + blockIdx.y] = fma(o.y_std, o.mean_constant + s, o.y_mean);
   }
@@ -100,16 +96,7 @@ static hipError_t launch_mean(const MeanArgs& a, hipStream_t s) {
   for (int i = 0; i < a.m; ++i) nmax = std::max(nmax, (int)a.outs.o[i].n);
   const size_t lds = mean_lds_bytes(nmax, a.d);
   const dim3 grid((a.P + PM_POINTS - 1) / PM_POINTS, a.m), block(PM_WAVES * WAVE);
-  auto go = [&](auto kern) {
-    raise_lds_limit(reinterpret_cast<const void*>(kern), lds);
-    hipLaunchKernelGGL(kern, grid, block, lds, s, a);
-  };
-  switch (dim_bucket(a.d)) {
-    case 2: go(posterior_mean_kernel<2>); break;
-    case 4: go(posterior_mean_kernel<4>); break;
-    case 8: go(posterior_mean_kernel<8>); break;
-    default: go(posterior_mean_kernel<16>); break;
-  }
+  by_dim(a.d, [&](auto dm) { launch_lds(posterior_mean_kernel<decltype(dm)::value>, grid, block, lds, s, a); });
   return hipGetLastError();
 }
 
@@ -311,13 +298,9 @@ static hipError_t launch_rank(const double* F, int S, int Q, int m, int keep, in
                               hipStream_t s) {
   const size_t lds = rank_lds_bytes(Q, m);
   const int nt = rank_threads(Q);
-  auto go = [&](auto kern) {
-    raise_lds_limit(reinterpret_cast<const void*>(kern), lds);
-    hipLaunchKernelGGL(kern, dim3(S), dim3(nt), lds, s, F, Q, m, keep, rank, crowd, order);
-  };
-  if (m <= 2) go(pareto_rank_kernel<2>);
-  else if (m <= 4) go(pareto_rank_kernel<4>);
-  else go(pareto_rank_kernel<8>);
+  by_objectives(m, [&](auto mb) {
+    launch_lds(pareto_rank_kernel<decltype(mb)::value>, dim3(S), dim3(nt), lds, s, F, Q, m, keep, rank, crowd, order);
+  });
   return hipGetLastError();
 }
 
@@ -345,11 +328,11 @@ struct WideWs {
 };
 __host__ inline WideWs wide_ws(int Q) {
   WideWs w{};
-  const size_t q = ((size_t)Q * sizeof(int) + 255) & ~(size_t)255;
-  w.cnt = 0;
-  w.rk = q;
-  w.scalars = 2 * q;
-  w.total = 2 * q + 256;
+  Carve c;
+  w.cnt = c.take((size_t)Q * sizeof(int));
+  w.rk = c.take((size_t)Q * sizeof(int));
+  w.scalars = c.take(256);
+  w.total = c.total();
   return w;
 }
 
@@ -543,29 +526,26 @@ __global__ __launch_bounds__(WR_WAVES* WAVE) void pareto_order_kernel(int Q, con
 static hipError_t launch_rank_wide(const double* F, int Q, int m, int keep, int* rank, double* crowd, int* order,
                                    void* work, hipStream_t s) {
   const WideWs w = wide_ws(Q);
-  char* ws = static_cast<char*>(work);
-  int* cnt = reinterpret_cast<int*>(ws + w.cnt);
-  int* rk = reinterpret_cast<int*>(ws + w.rk);
-  int* scalars = reinterpret_cast<int*>(ws + w.scalars);
+  int* cnt = at<int>(work, w.cnt);
+  int* rk = at<int>(work, w.rk);
+  int* scalars = at<int>(work, w.scalars);
   hipError_t e;
   hipLaunchKernelGGL(pareto_clear_kernel, dim3((std::max(Q, 64) + 255) / 256), dim3(256), 0, s, Q, cnt, rk, scalars,
                      order);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const dim3 dgrid((Q + PD_TILE - 1) / PD_TILE, (Q + PD_SLICE - 1) / PD_SLICE);
-  if (m <= 2) hipLaunchKernelGGL(pareto_dom_kernel<2>, dgrid, dim3(PD_TILE), 0, s, F, Q, m, cnt);
-  else if (m <= 4) hipLaunchKernelGGL(pareto_dom_kernel<4>, dgrid, dim3(PD_TILE), 0, s, F, Q, m, cnt);
-  else hipLaunchKernelGGL(pareto_dom_kernel<8>, dgrid, dim3(PD_TILE), 0, s, F, Q, m, cnt);
+  by_objectives(m, [&](auto mb) {
+    hipLaunchKernelGGL(pareto_dom_kernel<decltype(mb)::value>, dgrid, dim3(PD_TILE), 0, s, F, Q, m, cnt);
+  });
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const bool in_lds = peel_f_in_lds(Q, m);
   const size_t lds = peel_list_bytes(Q) + (in_lds ? (size_t)Q * m * sizeof(double) : 0);
   const int nt = std::min(1024, (Q + 63) / 64 * 64);
-  auto peel = [&](auto kern) {
-    raise_lds_limit(reinterpret_cast<const void*>(kern), lds);
-    hipLaunchKernelGGL(kern, dim3(1), dim3(nt), lds, s, F, Q, m, keep, (const int*)cnt, rk, scalars);
-  };
-  if (m <= 2) in_lds ? peel(pareto_peel_kernel<2, true>) : peel(pareto_peel_kernel<2, false>);
-  else if (m <= 4) in_lds ? peel(pareto_peel_kernel<4, true>) : peel(pareto_peel_kernel<4, false>);
-  else in_lds ? peel(pareto_peel_kernel<8, true>) : peel(pareto_peel_kernel<8, false>);
+  by_objectives(m, [&](auto mb) {
+    constexpr int MB = decltype(mb)::value;
+    launch_lds(in_lds ? pareto_peel_kernel<MB, true> : pareto_peel_kernel<MB, false>, dim3(1), dim3(nt), lds, s, F, Q,
+               m, keep, (const int*)cnt, rk, scalars);
+  });
   if ((e = hipGetLastError()) != hipSuccess) return e;
   const dim3 wgrid((Q + WR_WAVES - 1) / WR_WAVES), wblock(WR_WAVES * WAVE);
   hipLaunchKernelGGL(pareto_crowd_kernel, wgrid, wblock, 0, s, F, Q, m, (const int*)rk, rank, crowd);
@@ -857,19 +837,13 @@ namespace {
 
 int check_model(const dkg_output* outs, int m, int d) {
   if (!outs) return failf(DKG_ERR_ARG, "NULL pointer");
-  if (m < 1) return failf(DKG_ERR_ARG, "m=%d outputs", m);
-  if (m > DKG_MAX_OUTPUTS) return failf(DKG_ERR_UNSUPPORTED, "m=%d outputs (supported <= %d)", m, DKG_MAX_OUTPUTS);
-  if (d < 1) return failf(DKG_ERR_ARG, "d=%d", d);
-  if (d > DKG_MAX_DIM) return failf(DKG_ERR_UNSUPPORTED, "d=%d (supported 1..%d)", d, DKG_MAX_DIM);
-  for (int i = 0; i < m; ++i) {
-    if (outs[i].n < 1) return failf(DKG_ERR_ARG, "output %d: n=%d training points", i, outs[i].n);
-    if (outs[i].n > 1024) return failf(DKG_ERR_UNSUPPORTED, "output %d: n=%d > 1024 training points", i, outs[i].n);
-    if (outs[i].kernel < DKG_MATERN12 || outs[i].kernel > DKG_RBF)
-      return failf(DKG_ERR_ARG, "output %d: kernel id %d", i, outs[i].kernel);
-    if (!outs[i].inv_lengthscale || !outs[i].train_x || !outs[i].alpha)
-      return failf(DKG_ERR_ARG, "output %d: NULL pointer", i);
+  int st = check_dims(m, d);
+  for (int i = 0; i < m && !st; ++i) {
+    char who[32];
+    std::snprintf(who, sizeof who, "output %d", i);
+    st = check_output_state(outs[i], false, who);
   }
-  return DKG_OK;
+  return st;
 }
 
 int check_population(int P) {
@@ -947,21 +921,15 @@ struct GenWs {
 };
 GenWs gen_ws(int S, int P, int d, int m, bool wide) {
   GenWs w{};
-  size_t off = 0;
+  Carve c;
   const size_t q = (size_t)S * 2 * P;
-  w.x2 = off;
-  off = up256(off + q * d * sizeof(double));
-  w.f2 = off;
-  off = up256(off + q * m * sizeof(double));
-  w.crowd2 = off;
-  off = up256(off + q * sizeof(double));
-  w.rank2 = off;
-  off = up256(off + q * sizeof(int));
-  w.order = off;
-  off = up256(off + q * sizeof(int));
-  w.wide = off;
-  if (wide) off = up256(off + wide_ws(2 * P).total);
-  w.total = off;
+  w.x2 = c.take(q * d * sizeof(double));
+  w.f2 = c.take(q * m * sizeof(double));
+  w.crowd2 = c.take(q * sizeof(double));
+  w.rank2 = c.take(q * sizeof(int));
+  w.order = c.take(q * sizeof(int));
+  w.wide = c.take(wide ? wide_ws(2 * P).total : 0);
+  w.total = c.total();
   return w;
 }
 
@@ -979,7 +947,6 @@ int evolve(const Evaluator& ev, int S, int d, int m, bool wide, const double* lb
   if (!lb || !ub || !uniforms || !X || !F || !rank || !crowd || !work) return failf(DKG_ERR_ARG, "NULL pointer");
   const GenWs w = gen_ws(S, P, d, m, wide);
   if (work_bytes < w.total) return failf(DKG_ERR_WORKSPACE, "workspace %zu bytes < required %zu", work_bytes, w.total);
-  char* ws = static_cast<char*>(work);
   const size_t Pd = (size_t)P * d, Pm = (size_t)P * m, draws = dkg_pareto_draws(P, d);
   GenArgs g = gen_args(lb, ub, uniforms, P, d, m, prm);
   g.u_stride = Pd + (size_t)gens * draws;
@@ -987,12 +954,12 @@ int evolve(const Evaluator& ev, int S, int d, int m, bool wide, const double* lb
   g.F = F;
   g.crowd = crowd;
   g.rank = rank;
-  g.X2 = reinterpret_cast<double*>(ws + w.x2);
-  g.F2 = reinterpret_cast<double*>(ws + w.f2);
-  g.crowd2 = reinterpret_cast<double*>(ws + w.crowd2);
-  g.rank2 = reinterpret_cast<int*>(ws + w.rank2);
-  g.order = reinterpret_cast<int*>(ws + w.order);
-  void* wide_work = wide && S == 1 ? ws + w.wide : nullptr;
+  g.X2 = at<double>(work, w.x2);
+  g.F2 = at<double>(work, w.f2);
+  g.crowd2 = at<double>(work, w.crowd2);
+  g.rank2 = at<int>(work, w.rank2);
+  g.order = at<int>(work, w.order);
+  void* wide_work = wide && S == 1 ? at<char>(work, w.wide) : nullptr;
   const double *elb = prm->raw_inputs ? nullptr : lb, *eub = prm->raw_inputs ? nullptr : ub;
   // the Q = P or 2P points per sample of f, keep = P
   auto rank_step = [&](const double* f, int Q, int* rk, double* cd) {

@@ -16,7 +16,7 @@
 #include <atomic>
 #include <cmath>
 
-#include "dkg_kernels.h"
+#include "dkg_acq.h"
 
 namespace dkg {
 
@@ -266,16 +266,7 @@ hipError_t launch_rff_eval(const dkg_rff_paths& p, const double* x, size_t x_str
   const EvalArgs a{p, x, x_stride, F, f_stride, lb, ub, P};
   const size_t lds = DKG_RFF_EVAL_LDS_BYTES(a.p.R, a.p.d);
   const dim3 grid((a.P + RE_POINTS - 1) / RE_POINTS, a.p.m, a.p.S), block(RE_WAVES * WAVE);
-  auto go = [&](auto kern) {
-    raise_lds_limit(reinterpret_cast<const void*>(kern), lds);
-    hipLaunchKernelGGL(kern, grid, block, lds, s, a);
-  };
-  switch (dim_bucket(a.p.d)) {
-    case 2: go(rff_eval_kernel<2>); break;
-    case 4: go(rff_eval_kernel<4>); break;
-    case 8: go(rff_eval_kernel<8>); break;
-    default: go(rff_eval_kernel<16>); break;
-  }
+  by_dim(a.p.d, [&](auto dm) { launch_lds(rff_eval_kernel<decltype(dm)::value>, grid, block, lds, s, a); });
   return hipGetLastError();
 }
 
@@ -285,8 +276,8 @@ int check_rff_paths(const dkg_rff_paths* p) {
     return failf(DKG_ERR_ARG, "paths S=%d m=%d d=%d R=%d", p->S, p->m, p->d, p->R);
   if (p->S > DKG_JES_MAX_SAMPLES)
     return failf(DKG_ERR_UNSUPPORTED, "S=%d samples (supported <= %d)", p->S, DKG_JES_MAX_SAMPLES);
-  if (p->m > DKG_MAX_OUTPUTS) return failf(DKG_ERR_UNSUPPORTED, "m=%d outputs (supported <= %d)", p->m, DKG_MAX_OUTPUTS);
-  if (p->d > DKG_MAX_DIM) return failf(DKG_ERR_UNSUPPORTED, "d=%d (supported 1..%d)", p->d, DKG_MAX_DIM);
+  const int st = check_dims(p->m, p->d);
+  if (st) return st;
   if (p->R > RFF_MAXR) return failf(DKG_ERR_UNSUPPORTED, "R=%d features (supported <= %d)", p->R, RFF_MAXR);
   if (!p->omega || !p->bias || !p->coef || !p->offset) return failf(DKG_ERR_ARG, "paths: NULL pointer");
   return DKG_OK;
@@ -306,12 +297,12 @@ struct RffWs {
 };
 RffWs rff_ws(int R, int n_max) {
   RffWs w{};
-  const size_t rr = up256((size_t)R * R * sizeof(double));
+  Carve slot;  // a, x and phi are offsets within a slot
+  w.a = slot.take((size_t)R * R * sizeof(double));
+  w.x = slot.take((size_t)R * R * sizeof(double));
+  w.phi = slot.take((size_t)n_max * R * sizeof(double));
+  w.slot = slot.total();
   w.info = 0;
-  w.a = 0;
-  w.x = rr;
-  w.phi = 2 * rr;
-  w.slot = 2 * rr + up256((size_t)n_max * R * sizeof(double));
   w.total = 256 + RFF_NB * w.slot;
   return w;
 }
@@ -371,8 +362,7 @@ int dkg_rff_weights(const dkg_output* outs, int m, int d, const double* const* t
   const RffWs w = rff_ws(R, n_max);
   if (work_bytes < w.total) return failf(DKG_ERR_WORKSPACE, "workspace %zu bytes < required %zu", work_bytes, w.total);
   hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(work);
-  int* d_info = reinterpret_cast<int*>(ws + w.info);
+  int* d_info = at<int>(work, w.info);
   const int total = S * m;
   for (int q0 = 0; q0 < total; q0 += RFF_NB) {
     const int nb = std::min(RFF_NB, total - q0);
@@ -383,7 +373,7 @@ int dkg_rff_weights(const dkg_output* outs, int m, int d, const double* const* t
     int nbmax = 1;
     for (int j = 0; j < nb; ++j) {
       const int q = q0 + j, i = q % m;
-      char* slot = ws + 256 + (size_t)j * w.slot;
+      char* slot = at<char>(work, 256 + (size_t)j * w.slot);
       b.o[j] = outs[i];
       b.y[j] = train_y[i];
       b.wn[j] = wn + (size_t)q * R * d;
@@ -394,9 +384,9 @@ int dkg_rff_weights(const dkg_output* outs, int m, int d, const double* const* t
       b.bias[j] = paths->bias + (size_t)q * R;
       b.coef[j] = paths->coef + (size_t)q * R;
       b.offset[j] = paths->offset + q;
-      b.A[j] = reinterpret_cast<double*>(slot + w.a);
-      b.X[j] = reinterpret_cast<double*>(slot + w.x);
-      b.Phi[j] = reinterpret_cast<double*>(slot + w.phi);
+      b.A[j] = at<double>(slot, w.a);
+      b.X[j] = at<double>(slot, w.x);
+      b.Phi[j] = at<double>(slot, w.phi);
       b.info[j] = d_info + j;
       b.diag[j] = outs[i].noise;
       pb.A[j] = b.A[j];

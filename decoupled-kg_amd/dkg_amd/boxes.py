@@ -21,7 +21,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from .errors import UnsupportedError
+from ._plan import hip_device, workspace
 from .gp_state import current_stream_ptr
 
 NEG_INF = -1e10  # the reference point of the JES box decompositions (jes.NEG_INF)
@@ -30,18 +30,6 @@ NEG_INF = -1e10  # the reference point of the JES box decompositions (jes.NEG_IN
 def box_count_bound(K: int, m: int) -> int:
     """The most boxes K points of m objectives give (include/dkg.h): 1, K and 2K - 1 at m = 1, 2 and 3."""
     return 1 if m == 1 else (K if m == 2 else 2 * K - 1)
-
-
-def _device(device, *tensors) -> torch.device:
-    if device is None:
-        for t in tensors:
-            if t.device.type == "cuda":
-                return t.device
-        return torch.device("cuda", torch.cuda.current_device())
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise UnsupportedError("the box kernels run on a ROCm (HIP) device; got " + str(dev))
-    return dev
 
 
 def _ref_array(ref: Sequence[float], m: int):
@@ -61,8 +49,7 @@ def dominated_boxes_device(Y: Tensor, ref_point: Sequence[float], J: Optional[in
         J = box_count_bound(K, m)
     bounds = torch.empty(S, 2, max(J, 0), m, dtype=torch.double, device=Y.device)
     count = torch.empty(S, dtype=torch.int32, device=Y.device)
-    need = lib.dkg_dominated_boxes_workspace(S, K, m)
-    work = torch.empty(max(need, 256), dtype=torch.uint8, device=Y.device)
+    work = workspace(lib.dkg_dominated_boxes_workspace(S, K, m), Y.device)
     with torch.cuda.device(Y.device):
         _lib.check(lib.dkg_dominated_boxes(_lib.ptr(Y), S, K, m, _ref_array(ref_point, m), int(J), _lib.ptr(bounds),
                                            _lib.ptr(count), _lib.ptr(work), work.numel(),
@@ -84,7 +71,7 @@ def dominated_boxes(pareto_fronts: List[Tensor], maximize: bool = True, ref_poin
     m = pareto_fronts[0].shape[-1]
     if not all(pf.shape[-1] == m and pf.shape[0] >= 1 for pf in pareto_fronts):
         raise ValueError("Expected every Pareto front to hold at least one point of the same number of objectives.")
-    dev = _device(device, *pareto_fronts)
+    dev = hip_device(device, "box", *pareto_fronts)
     weight = 1.0 if maximize else -1.0
     if ref_point is None:
         ref = torch.full((m,), NEG_INF, dtype=torch.double)
@@ -114,8 +101,7 @@ def hypervolume_front_device(Y: Tensor, ref_point: Sequence[float]) -> Tensor:
     S, K, m = Y.shape
     Y = Y.contiguous()
     hv = torch.empty(S, dtype=torch.double, device=Y.device)
-    need = lib.dkg_hypervolume_front_workspace(S, K, m)
-    work = torch.empty(max(need, 256), dtype=torch.uint8, device=Y.device)
+    work = workspace(lib.dkg_hypervolume_front_workspace(S, K, m), Y.device)
     with torch.cuda.device(Y.device):
         _lib.check(lib.dkg_hypervolume_front(_lib.ptr(Y), S, K, m, _ref_array(ref_point, m), _lib.ptr(hv),
                                              _lib.ptr(work), work.numel(), current_stream_ptr(Y.device)),
@@ -133,7 +119,7 @@ def hypervolume_front(points, ref_point, device=None) -> Tensor:
     ref = torch.as_tensor(ref_point).detach().to("cpu", torch.double).reshape(-1)
     if ref.shape[0] != P.shape[-1]:
         raise ValueError(f"Expected ref_point of {P.shape[-1]} entries. Got {ref.shape[0]}.")
-    dev = _device(device, P)
+    dev = hip_device(device, "box", P)
     Y = P.detach().to(dev, torch.double)
     if P.shape[-2] == 0:
         return torch.zeros(P.shape[:-2], dtype=torch.double, device=dev)

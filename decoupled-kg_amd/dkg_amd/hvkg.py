@@ -28,7 +28,7 @@ from typing import Optional, Sequence
 import torch
 from torch import Tensor
 
-from . import _lib
+from . import _lib, _plan
 from .discretekg import _as_model_state, _Base, _fingerprint, _HAVE_BOTORCH, shared_state
 from .errors import UnsupportedError
 from .gp_state import current_stream_ptr
@@ -48,20 +48,18 @@ def hypervolume_limits(m: int, num_fantasies: int, num_pareto: int) -> None:
         raise UnsupportedError(f"num_pareto={num_pareto} > {_lib.DKG_HVKG_MAX_PARETO}")
 
 
-class HvkgPlan:
+class HvkgPlan(_plan.Plan):
     """A ``dkg_hvkg_*`` plan (include/dkg.h): the outputs, the reference point, the base samples, the mask and the
     two scalars, with the workspace for up to ``max_B`` restarts.  ``mask = 0`` is the value function."""
 
     def __init__(self, structs, m: int, d: int, ref_point, num_fantasies: int, num_pareto: int, base_samples,
                  mask: int, current_value: float, cost: float, max_B: int, device):
         lib = _lib.load()
-        self.device = device
-        self.m, self.d, self.max_B = m, d, int(max_B)
+        self.m, self.d = m, d
         self.Nf, self.Np = int(num_fantasies), int(num_pareto)
         self.rows = self.Nf * self.Np + (1 if mask else 0)
-        self.host = ctypes.create_string_buffer(lib.dkg_hvkg_plan_bytes())
-        need = lib.dkg_hvkg_workspace(m, d, self.Nf, self.Np, self.max_B)
-        self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+        super().__init__(device, lib.dkg_hvkg_plan_bytes(),
+                         lib.dkg_hvkg_workspace(m, d, self.Nf, self.Np, int(max_B)), max_B)
         ref = (ctypes.c_double * m)(*[float(v) for v in ref_point])
         z = None
         if mask:
@@ -76,13 +74,8 @@ class HvkgPlan:
         ``out[:B]`` the values, ``out[B:]`` dacq/dX row-major; else ``[B]``) and, with ``means``, the fantasised
         means ``[B, Nf, Np, m]``."""
         B = X.shape[0]
-        X = X.contiguous()
-        n = self.rows * self.d
-        out = torch.empty(B * (1 + n) if grad else B, dtype=torch.double, device=self.device)
         Y = torch.empty(B, self.Nf, self.Np, self.m, dtype=torch.double, device=self.device) if means else None
-        dacq = out.data_ptr() + 8 * B if grad else 0
-        _lib.check(self._fwd(self.host, _lib.ptr(X), B, _lib.ptr(out), dacq, _lib.ptr(Y),
-                             current_stream_ptr(self.device)), "dkg_hvkg_forward")
+        out = self._forward(self._fwd, "dkg_hvkg_forward", X, self.rows * self.d, grad, Y)
         return (out, Y) if means else out
 
 
@@ -103,45 +96,6 @@ def hypervolume_device(Y: Tensor, ref_point, grad: bool = False):
     return (hv, dhv) if grad else hv
 
 
-class _ForwardFn(torch.autograd.Function):
-    """Device points ``[B, rows, d]``; with a gradient the same call also returns dacq(X_b)/dX_b, and backward
-    scales it by the incoming gradient (acq(X_b) depends on X_b only)."""
-
-    @staticmethod
-    def forward(ctx, X, acq):
-        B = X.shape[0]
-        if ctx.needs_input_grad[0]:
-            out = acq._plan_for(B, X.shape[1]).forward(X, grad=True)
-            ctx.save_for_backward(out[B:].view(X.shape))
-            return out[:B]
-        return acq._plan_for(B, X.shape[1]).forward(X)
-
-    @staticmethod
-    def backward(ctx, grad):
-        (dacq,) = ctx.saved_tensors
-        return grad.to(dacq)[:, None, None] * dacq, None
-
-
-class _HostForwardFn(torch.autograd.Function):
-    """Host points ``[*batch, rows, d]`` (what ``optimize_acqf`` passes): one copy each way, a host backward.  The
-    same kernels as ``_ForwardFn``, so the same bits."""
-
-    @staticmethod
-    def forward(ctx, X, acq):
-        if ctx.needs_input_grad[0]:
-            val, dacq = acq.value_and_grad_host(X)
-            ctx.save_for_backward(dacq)
-            ctx.xdtype = X.dtype
-            return val.to(X.dtype)
-        return acq._values_host(X).to(X.dtype)
-
-    @staticmethod
-    def backward(ctx, grad):
-        (dacq,) = ctx.saved_tensors  # shaped as X
-        out = grad.to(dacq).reshape(grad.shape + (1, 1)) * dacq
-        return out.to(ctx.xdtype), None
-
-
 class _HypervolumeBase(_Base):
     """What the two acquisitions share: the model read live (``_fingerprint``), its device state shared through
     ``shared_state`` over an empty discretisation, the plan cache and the two evaluation routes."""
@@ -160,9 +114,7 @@ class _HypervolumeBase(_Base):
                 f"The length of the reference point must match the number of outcomes. Got ref_point with "
                 f"{ref.shape[0]} elements, but expected {self._m}.")
         self.ref_point = ref
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if dev.type != "cuda":
-            raise UnsupportedError("the hypervolume kernels run on a ROCm (HIP) device; got " + str(dev))
+        dev = _plan.hip_device(device, "hypervolume")
         if self._d > _lib.MAX_DIM:
             raise UnsupportedError(f"input dimension {self._d} > {_lib.MAX_DIM}")
         self._device = dev
@@ -191,12 +143,10 @@ class _HypervolumeBase(_Base):
         key, Nf, Np, z, mask, current, cost = self._plan_args(rows)
         plan = self._plans.get(key)
         if plan is None or plan.max_B < B:
-            cap = MIN_PLAN_RESTARTS
-            while cap < B:
-                cap *= 2
+            cap = _plan.grow(B, MIN_PLAN_RESTARTS, _lib.DKG_HVKG_MAX_RESTARTS)
             with torch.cuda.device(self._device):
                 plan = HvkgPlan(self._state.structs, self._m, self._d, self.ref_point.tolist(), Nf, Np, z, mask,
-                                current, cost, min(cap, _lib.DKG_HVKG_MAX_RESTARTS), self._device)
+                                current, cost, cap, self._device)
             self._plans[key] = plan
         return plan
 
@@ -217,10 +167,10 @@ class _HypervolumeBase(_Base):
         if X.dim() == 2:
             X = X.unsqueeze(0)
         if X.device.type == "cpu":
-            return _HostForwardFn.apply(X, self)
+            return _plan.HostForwardFn.apply(X, self)
         batch = X.shape[:-2]
         Xd = X.reshape((-1,) + tuple(X.shape[-2:])).to(self._device, torch.double)
-        return _ForwardFn.apply(Xd, self).to(device=X.device, dtype=X.dtype).reshape(batch)
+        return _plan.ForwardFn.apply(Xd, self).to(device=X.device, dtype=X.dtype).reshape(batch)
 
     def _host_x(self, X: Tensor):
         self._check_x(X)

@@ -19,13 +19,12 @@ launches through the C ABI (``include/dkg.h`` ``dkg_jes_*``).  The
 
 from __future__ import annotations
 
-import ctypes
 from typing import List, Optional
 
 import torch
 from torch import Tensor
 
-from . import _lib, gp_state
+from . import _lib, _plan, gp_state
 from .discretekg import _as_model_state, _Base, _HAVE_BOTORCH, t_batch_mode_transform
 from .errors import UnsupportedError
 from .gp_state import current_stream_ptr
@@ -116,77 +115,30 @@ def conditioned_states(state: ModelListGPState, pareto_sets, pareto_fronts) -> L
     return out
 
 
-class JesPlan:
+class JesPlan(_plan.Plan):
     """A ``dkg_jes_*`` plan (include/dkg.h): the (P + 1) m fitted states, the boxes, the estimator and the
     target, with the workspace for up to ``max_B`` candidates; the state table is uploaded once."""
 
     def __init__(self, structs, m: int, P: int, d: int, bounds: Tensor, target: int, only_diagonal: bool,
                  max_B: int, device):
         lib = _lib.load()
-        self.device = device
-        self.m, self.P, self.d, self.max_B = m, P, d, int(max_B)
+        self.m, self.P, self.d = m, P, d
         self.J = bounds.shape[2]
         self.bounds = bounds  # device [P, 2, J, m]; read at every evaluation
-        self.host = ctypes.create_string_buffer(lib.dkg_jes_plan_bytes())
-        need = lib.dkg_jes_workspace(m, P, d, self.J, self.max_B)
-        self.ws = torch.empty(max(need, 256), dtype=torch.uint8, device=device)
+        super().__init__(device, lib.dkg_jes_plan_bytes(), lib.dkg_jes_workspace(m, P, d, self.J, int(max_B)), max_B)
         _lib.check(lib.dkg_jes_init(structs, m, P, d, _lib.ptr(bounds), self.J, target, int(bool(only_diagonal)),
                                     self.max_B, _lib.ptr(self.ws), self.ws.numel(), self.host,
                                     current_stream_ptr(device)), "dkg_jes_init")
         self._fwd = lib.dkg_jes_forward
 
     def forward(self, X: Tensor, grad: bool = False, moments: bool = False):
-        """``X``: device fp64 ``[B, d]``.  -> ``out`` (device, ``[B * (1 + d)]`` with the gradient, else
-        ``[B]``: ``out[:B]`` the values, ``out[B:]`` dacq/dX row-major) and, with ``moments``, the exported
-        moments ``[3, P + 1, m, B]``."""
+        """``X``: device fp64 ``[B, d]`` or ``[B, 1, d]``.  -> ``out`` (device, ``[B * (1 + d)]`` with the
+        gradient, else ``[B]``: ``out[:B]`` the values, ``out[B:]`` dacq/dX row-major) and, with ``moments``, the
+        exported moments ``[3, P + 1, m, B]``."""
         B = X.shape[0]
-        X = X.contiguous()
-        out = torch.empty(B * (1 + self.d) if grad else B, dtype=torch.double, device=self.device)
         mom = torch.empty(3, self.P + 1, self.m, B, dtype=torch.double, device=self.device) if moments else None
-        dacq = out.data_ptr() + 8 * B if grad else 0
-        _lib.check(self._fwd(self.host, _lib.ptr(X), B, _lib.ptr(out), dacq, _lib.ptr(mom),
-                             current_stream_ptr(self.device)), "dkg_jes_forward")
+        out = self._forward(self._fwd, "dkg_jes_forward", X, self.d, grad, mom)
         return (out, mom) if moments else out
-
-
-class _ForwardFn(torch.autograd.Function):
-    """Device candidates ``[B, d]``; with a gradient the same call also returns dacq(x_b)/dx_b, and backward
-    scales it by the incoming gradient (acq(x_b) depends on x_b only: the Jacobian is block diagonal)."""
-
-    @staticmethod
-    def forward(ctx, X, acq):
-        B, d = X.shape
-        if ctx.needs_input_grad[0]:
-            out = acq._plan_for(B).forward(X, grad=True)
-            ctx.save_for_backward(out[B:].view(B, d))
-            return out[:B]
-        return acq._plan_for(B).forward(X)
-
-    @staticmethod
-    def backward(ctx, grad):
-        (dacq,) = ctx.saved_tensors
-        return grad.to(dacq)[:, None] * dacq, None
-
-
-class _HostForwardFn(torch.autograd.Function):
-    """Host candidates ``[*batch, 1, d]`` (what ``optimize_acqf`` passes): one copy each way, a host backward,
-    and the autograd graph is this one node.  The same kernels as ``_ForwardFn``, so the same bits."""
-
-    @staticmethod
-    def forward(ctx, X, acq):
-        batch = X.shape[:-2]
-        if ctx.needs_input_grad[0]:
-            val, dacq = acq.value_and_grad_host(X)
-            ctx.save_for_backward(dacq)
-            ctx.xdtype = X.dtype
-            return val.to(X.dtype)
-        return acq._values_host(X).to(X.dtype).reshape(batch)
-
-    @staticmethod
-    def backward(ctx, grad):
-        (dacq,) = ctx.saved_tensors  # shaped as X
-        out = grad.to(dacq).reshape(grad.shape + (1, 1)) * dacq
-        return out.to(ctx.xdtype), None
 
 
 class qLowerBoundMultiObjectiveJointEntropySearch(_Base):
@@ -259,9 +211,7 @@ class qLowerBoundMultiObjectiveJointEntropySearch(_Base):
                 self._target = t % m
             else:
                 self._target_error = IndexError("list index out of range")
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if dev.type != "cuda":
-            raise UnsupportedError("the joint entropy search kernels run on a ROCm (HIP) device; got " + str(dev))
+        dev = _plan.hip_device(device, "joint entropy search")
         if m > _lib.MAX_OUTPUTS:
             raise UnsupportedError(f"{m} outputs > {_lib.MAX_OUTPUTS}")
         if d > _lib.MAX_DIM:
@@ -285,18 +235,15 @@ class qLowerBoundMultiObjectiveJointEntropySearch(_Base):
             raise UnsupportedError(f"{type(self).__name__} does not account for X_pending yet.")
         self.X_pending = None
 
-    def _plan_for(self, B: int) -> JesPlan:
-        """The plan, grown (powers of two, at least 16) to hold B candidates."""
+    def _plan_for(self, B: int, rows: int = 1) -> JesPlan:
+        """The plan, grown (powers of two, at least 16) to hold B candidates (of ``rows`` = 1 point each)."""
         if self._target_error is not None:
             raise self._target_error
         if self._plan is None or self._plan.max_B < B:
-            cap = 16
-            while cap < B:
-                cap *= 2
             with torch.cuda.device(self._device):
                 self._plan = JesPlan(self._structs, self._m, self._P, self._d, self._bounds,
                                      -1 if self._target is None else self._target, self.estimation_type == "LB2",
-                                     cap, self._device)
+                                     _plan.grow(B), self._device)
         return self._plan
 
     def _check_d(self, X: Tensor) -> None:
@@ -307,10 +254,10 @@ class qLowerBoundMultiObjectiveJointEntropySearch(_Base):
     def forward(self, X: Tensor) -> Tensor:
         self._check_d(X)
         if X.device.type == "cpu":
-            return _HostForwardFn.apply(X, self)
+            return _plan.HostForwardFn.apply(X, self)
         batch = X.shape[:-2]
-        Xd = X.reshape(-1, self._d).to(self._device, torch.double)
-        return _ForwardFn.apply(Xd, self).to(device=X.device, dtype=X.dtype).reshape(batch)
+        Xd = X.reshape(-1, 1, self._d).to(self._device, torch.double)
+        return _plan.ForwardFn.apply(Xd, self).to(device=X.device, dtype=X.dtype).reshape(batch)
 
     def _host_x(self, X: Tensor):
         self._check_d(X)

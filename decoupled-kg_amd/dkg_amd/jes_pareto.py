@@ -29,10 +29,11 @@ import torch
 from torch import Tensor
 
 from . import _lib
+from ._plan import hip_device, workspace
 from .errors import UnsupportedError
 from .gp_state import _base_struct, current_stream_ptr
 from .model import ModelListGPState, SingleTaskGPState
-from .pareto import _device, _evolve, pareto_draws
+from .pareto import _evolve, pareto_draws
 
 # the reference's variation (jes_sample_pareto.py:200-201): SimulatedBinaryCrossover(prob=0.9, eta=15),
 # PolynomialMutation(eta=20); the per-coordinate mutation probability is pymoo's default, min(0.5, 1 / d)
@@ -112,7 +113,7 @@ class RffPaths:
 def rff_weights(model, wn, g, ub, z, device=None, max_tries: int = 3) -> RffPaths:
     """``dkg_rff_weights`` on the caller's draws (shapes of ``draw_rff_randomness``)."""
     state = _model_state(model)
-    dev = _device(device)
+    dev = hip_device(device, "Pareto")
     m, d = state.num_outputs, state.input_dim
     S, mm, R, dd = wn.shape
     if mm != m or dd != d:
@@ -137,7 +138,7 @@ def rff_weights(model, wn, g, ub, z, device=None, max_tries: int = 3) -> RffPath
     offset = torch.empty(S, m, dtype=torch.double, device=dev)
     paths = RffPaths(omega, bias, coef, offset)
     nbytes = int(lib.dkg_rff_workspace(R, n_max))  # 0 outside the limits: the call below reports which
-    work = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    work = workspace(nbytes, dev)
     jit = (ctypes.c_double * (S * m))()
     outs = (_lib.DkgOutput * m)(*structs)
     with torch.cuda.device(dev):
@@ -203,7 +204,7 @@ def prune_pareto_front(pareto_set, pareto_front, num_points: int, device=None):
     as_numpy = not isinstance(pareto_front, torch.Tensor)
     ps = torch.as_tensor(pareto_set, dtype=torch.double)
     pf = torch.as_tensor(pareto_front, dtype=torch.double)
-    dev = pf.device if pf.is_cuda and device is None else _device(device)
+    dev = pf.device if pf.is_cuda and device is None else hip_device(device, "Pareto")
     if pf.dim() != 2 or ps.dim() != 2 or ps.shape[0] != pf.shape[0]:
         raise ValueError("pareto_set must be Q x d and pareto_front Q x m")
     if pf.shape[0] == 0:

@@ -23,6 +23,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._plan import hip_device
+from ._plan import workspace as _workspace
 from .errors import UnsupportedError
 from .gp_state import current_stream_ptr, prepare_outputs
 from .model import ModelListGPState, SingleTaskGPState
@@ -31,21 +33,12 @@ N_PARETO_POINTS = 100  # performance_after_scalarisation.py:14 under SMOKE_TEST 
 N_GENERATIONS = 100  # pygmo.nsga2(gen=100), sample.py:41
 
 
-def _device(device) -> torch.device:
-    if device is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise UnsupportedError("the Pareto kernels run on a ROCm (HIP) device; got " + str(device))
-    return device
-
-
 class PreparedModel:
     """A model's device caches for ``dkg_posterior_mean`` (``prepare_outputs`` over an empty discretisation: the
     factorisation and alpha, no Q_D)."""
 
     def __init__(self, model, device=None):
-        self.device = _device(device)
+        self.device = hip_device(device, "Pareto")
         if isinstance(model, SingleTaskGPState):
             model = ModelListGPState(model)
         self.model = model
@@ -91,7 +84,7 @@ def nondominated_rank(F, keep: Optional[int] = None, device=None):
     the ranked points by (rank, crowding descending, index), then -1.  Q <= 16384: the call brings the workspace
     ``dkg_pareto_rank_workspace`` asks for, so the library ranks Q <= 2048 points with whichever of its two paths
     its rule names and more points with the wide one; the results do not depend on the path."""
-    dev = F.device if isinstance(F, torch.Tensor) and F.is_cuda and device is None else _device(device)
+    dev = F.device if isinstance(F, torch.Tensor) and F.is_cuda and device is None else hip_device(device, "Pareto")
     F = torch.as_tensor(F, dtype=torch.double).detach().to(dev).contiguous()
     if F.dim() != 2:
         raise ValueError("F must be Q x m")
@@ -193,7 +186,7 @@ def _evolve(entry: str, model_args: tuple, workspace: str, dev, lead: tuple, d: 
     rank = torch.empty(*rows, dtype=torch.int32, device=dev)
     crowd = torch.empty(*rows, dtype=torch.double, device=dev)
     nbytes = int(getattr(lib, workspace)(*lead, P, d, mo))
-    work = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    work = _workspace(nbytes, dev)
     with torch.cuda.device(dev):
         _lib.check(getattr(lib, entry)(*model_args, _lib.ptr(lb), _lib.ptr(ub), P, gens, prm, _lib.ptr(uniforms),
                                        _lib.ptr(X), _lib.ptr(F), _lib.ptr(rank), _lib.ptr(crowd), _lib.ptr(work),
