@@ -1,6 +1,7 @@
 // What the acquisition and metric translation units share (dkg_pareto, dkg_jes, dkg_rff, dkg_hvkg, dkg_boxes): the
 // dispatch from a run-time covariance family, input dimension or objective count to a kernel instantiation, a point
-// scaled into registers and its padded distance, the workspace carve and the argument checks of a fitted output.
+// scaled into registers and its padded distance, and the argument checks of a fitted output (the workspace carve is
+// dkg_kernels.h's).
 // Every device helper runs the operations its call sites ran, in their order.
 #pragma once
 
@@ -73,22 +74,6 @@ void by_objectives(int m, F&& f) {
   if (m <= 2) f(std::integral_constant<int, 2>{});
   else if (m <= 4) f(std::integral_constant<int, 4>{});
   else f(std::integral_constant<int, 8>{});
-}
-
-// A workspace carve: take(bytes) is the offset of the next section and moves on by bytes rounded up to `align`
-struct Carve {
-  size_t off = 0;
-  size_t take(size_t bytes, size_t align = 256) {
-    const size_t at = off;
-    off = (off + bytes + align - 1) & ~(align - 1);
-    return at;
-  }
-  size_t total() const { return off; }
-};
-
-template <class T>
-T* at(void* base, size_t off) {
-  return reinterpret_cast<T*>(static_cast<char*>(base) + off);
 }
 
 // The limits on the output count and the input dimension

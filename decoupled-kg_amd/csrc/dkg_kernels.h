@@ -231,13 +231,27 @@ hipError_t launch_forward(const Plan& host, const Plan* dev, const double* xnew,
 // otherwise the three stage kernels.  Same bits.
 // Dynamic LDS bytes of the fused forward for a plan (dkg_fused.h fused_lds_bytes).
 size_t fused_lds_bytes_host(const Plan& h);
-// Sets dkg_last_error()'s thread-local message (host translation units other than dkg_abi.hip); returns code.
-int report_error(int code, const char* msg);
-// The same with a printf-style message; a hipError_t as a status (DKG_OK, or DKG_ERR_HIP and "what: the runtime's
-// text"); the 256-byte rounding of the workspace carves.  Defined once, in dkg_abi.hip.
+// Sets dkg_last_error()'s thread-local message, printf-style (at most 511 bytes), and returns code; a hipError_t as
+// a status (DKG_OK, or DKG_ERR_HIP and "what: the runtime's text"); the 256-byte rounding of the workspace carves.
+// Every host translation unit reports through these; defined once, in dkg_abi.hip.
 int failf(int code, const char* fmt, ...);
 int hip_status(hipError_t e, const char* what);
 size_t up256(size_t x);
+// A workspace carve: take(bytes) is the offset of the next section and moves on by bytes rounded up to `align`
+// (from an aligned offset that is up256(off + bytes), and take(0) does not move)
+struct Carve {
+  size_t off = 0;
+  size_t take(size_t bytes, size_t align = 256) {
+    const size_t at = off;
+    off = (off + bytes + align - 1) & ~(align - 1);
+    return at;
+  }
+  size_t total() const { return off; }
+};
+template <class T>
+T* at(void* base, size_t off) {
+  return reinterpret_cast<T*>(static_cast<char*>(base) + off);
+}
 // dkg_rff.hip.  The argument check of a dkg_rff_paths, and the values of its S paths: sample s's points [P][d] at
 // x + s * x_stride (0: every sample evaluates the same points) into F + s * f_stride [P][m]; lb / ub not NULL: the
 // model input is unit_cube(x, lb, ub).

@@ -11,10 +11,8 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
-#include <cstdarg>
 #include <chrono>
 #include <condition_variable>
-#include <cstdio>
 #include <mutex>
 #include <new>
 #include <thread>
@@ -26,15 +24,6 @@
 namespace dkg {
 
 namespace {
-
-int fail(int code, const char* fmt, ...) {
-  char buf[256];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return report_error(code, buf);
-}
 
 struct Launcher {
   int nthreads = 1;  // including the caller
@@ -113,10 +102,10 @@ using dkg::Launcher;
 extern "C" {
 
 int dkg_launcher_create(int threads, void** out) {
-  if (!out) return dkg::fail(DKG_ERR_ARG, "NULL handle pointer");
-  if (threads < 1 || threads > 64) return dkg::fail(DKG_ERR_ARG, "launcher threads=%d (1..64)", threads);
+  if (!out) return dkg::failf(DKG_ERR_ARG, "NULL handle pointer");
+  if (threads < 1 || threads > 64) return dkg::failf(DKG_ERR_ARG, "launcher threads=%d (1..64)", threads);
   Launcher* L = new (std::nothrow) Launcher();
-  if (!L) return dkg::fail(DKG_ERR_HIP, "out of host memory");
+  if (!L) return dkg::failf(DKG_ERR_HIP, "out of host memory");
   L->nthreads = threads;
   for (int t = 1; t < threads; ++t) L->workers.emplace_back([L, t] { L->worker(t); });
   *out = L;
@@ -125,7 +114,7 @@ int dkg_launcher_create(int threads, void** out) {
 
 int dkg_launcher_arm(void* h, double seconds) {
   Launcher* L = static_cast<Launcher*>(h);
-  if (!L) return dkg::fail(DKG_ERR_ARG, "NULL launcher");
+  if (!L) return dkg::failf(DKG_ERR_ARG, "NULL launcher");
   const int64_t until = Launcher::now_ns() + (int64_t)(seconds > 0 ? seconds * 1e9 : 0);
   L->spin_until_ns.store(until, std::memory_order_relaxed);
   {
@@ -137,11 +126,11 @@ int dkg_launcher_arm(void* h, double seconds) {
 
 int dkg_launcher_graphs(void* h, int n_streams, void* const* streams, const int* offs, void* const* graphs) {
   Launcher* L = static_cast<Launcher*>(h);
-  if (!L) return dkg::fail(DKG_ERR_ARG, "NULL launcher");
+  if (!L) return dkg::failf(DKG_ERR_ARG, "NULL launcher");
   if (n_streams < 0 || (n_streams > 0 && (!streams || !offs || !graphs)))
-    return dkg::fail(DKG_ERR_ARG, "bad launcher arguments");
+    return dkg::failf(DKG_ERR_ARG, "bad launcher arguments");
   for (int s = 0; s < n_streams; ++s)
-    if (offs[s + 1] < offs[s]) return dkg::fail(DKG_ERR_ARG, "graph offsets not increasing at stream %d", s);
+    if (offs[s + 1] < offs[s]) return dkg::failf(DKG_ERR_ARG, "graph offsets not increasing at stream %d", s);
   std::lock_guard<std::mutex> call(L->call_mu);
   L->n_streams = n_streams;
   L->streams = streams;
@@ -158,7 +147,7 @@ int dkg_launcher_graphs(void* h, int n_streams, void* const* streams, const int*
   L->run_share(0);
   while (L->pending.load(std::memory_order_acquire) > 0) __builtin_ia32_pause();
   const int e = L->first_err.load(std::memory_order_relaxed);
-  if (e) return dkg::fail(DKG_ERR_HIP, "hipGraphLaunch: %s", hipGetErrorString((hipError_t)e));
+  if (e) return dkg::failf(DKG_ERR_HIP, "hipGraphLaunch: %s", hipGetErrorString((hipError_t)e));
   return DKG_OK;
 }
 

@@ -1,11 +1,14 @@
 """Bit-identity of two builds of libdkg.so (DKG_LIB A/B): forward KG, KG per pair and the value+gradient
 path on several workloads, then the acquisition layer (posterior mean, sample paths, NSGA-II, ranks, JES, HVKG,
-boxes) at small ragged shapes in every dimension bucket and covariance family.
+boxes) at small ragged shapes in every dimension bucket and covariance family, then the core entries' host side
+(state preparation with a jitter retry inside the batch, the MLL, an append, and plans that take every section of
+the plan workspace).
 
-Run on the GPU box from the repo root:  python tools/ab_bits.py <libA.so> <libB.so> [--acq-only] [--json OUT]
+Run on the GPU box from the repo root:
+    python tools/ab_bits.py <libA.so> <libB.so> [--acq-only|--core-only] [--json OUT]
 Each build runs in its own subprocess under a time limit (the library is loaded once per process), the second
 only after the first ended well; prints, per output, whether the two builds agree bit for bit, and with --json
-writes the table.  --acq-only skips the KG workloads.
+writes the table.  --acq-only skips the KG workloads, --core-only runs the core entries alone.
 """
 import json
 import os
@@ -87,6 +90,71 @@ def dump_acquisition(out):
         out[f"acq/boxes-m{m}/hypervolume_front"] = hypervolume_front_device(Y, ref).cpu()
 
 
+def dump_core(out):
+    """What a host-side change of csrc/dkg_abi.hip can move without changing a workspace size: an interior offset of
+    the plan, MLL or append workspace, or the sequence of the batched factorisation.  State, MLL and append at
+    n = (37, 36, 16), the third output needing the first jitter; the plans at n = (37, 36, 35), B = 17."""
+    import torch
+
+    from dkg_amd.fit import DeviceMll
+    from dkg_amd.gp_state import DeviceGPState
+    from dkg_amd.model import ModelListGPState, SingleTaskGPState
+
+    dev, d = torch.device("cuda", 0), 3
+    g = torch.Generator().manual_seed(2024)
+    rnd = lambda *shape: torch.rand(*shape, generator=g, dtype=torch.double)  # noqa: E731
+    randn = lambda n: torch.randn(n, generator=g, dtype=torch.double)  # noqa: E731
+    Xj = rnd(12, d)
+    Xj = torch.cat([Xj, Xj[:4]])  # duplicated inputs under a slightly negative shift (tests/test_gpu_state.py)
+    first = [SingleTaskGPState(rnd(37, d), randn(37), 0.3 + rnd(d), 2.0, 1e-3, 0.1, "matern", 2.5),
+             SingleTaskGPState(rnd(36, d), randn(36), 0.3 + rnd(d), 0.7, 1e-4, -0.3, "rbf")]
+    jittered = first + [SingleTaskGPState(Xj, randn(16), 0.5, 1.0, -5e-9, 0.0)]
+    plain = first + [SingleTaskGPState(rnd(35, d), randn(35), 0.3 + rnd(d), 1.3, 1e-2, 0.2, "matern", 1.5)]
+    D = rnd(50, d)
+
+    def caches(key, outputs):
+        for i, c in enumerate(outputs):
+            for name in ("L", "Linv", "alpha", "root_frag", "disc_frag", "disc_mean"):
+                out[f"{key}/{i}/{name}"] = getattr(c, name).cpu()
+            out[f"{key}/{i}/jitter"] = torch.tensor([c.jitter], dtype=torch.double)
+
+    state = DeviceGPState(ModelListGPState(*jittered), D, dev)
+    assert state.outputs[2].jitter > 0.0 and state.outputs[0].jitter == 0.0, "the retry did not run inside the batch"
+    caches("core/state", state.outputs)
+    mll = DeviceMll([s.train_x for s in jittered], [s.train_y for s in jittered], [2.5, float("inf"), 2.5], dev)
+    for name, a in zip(("value", "grad", "jitter"), mll.evaluate(
+            [s.mean_constant for s in jittered], [s.lengthscale.tolist() for s in jittered],
+            [s.outputscale for s in jittered], [s.noise for s in jittered])):
+        out["core/mll/" + name] = torch.from_numpy(a)
+    assert out["core/mll/jitter"][2] > 0.0
+    caches("core/append", [state.with_observation(0, rnd(d), y=0.3).outputs[0]])
+
+    X = rnd(17, d).to(dev)
+    W = lambda S: 0.1 + rnd(S, 3)  # noqa: E731
+    st = DeviceGPState(ModelListGPState(*plain), D, dev)
+    out["core/f32/kg"] = st.plan(W(3), None, 17, f32=True).forward(X).cpu()
+    every = [None, 0, 1, 2]
+    for part, t in zip(("kg", "pairs", "hull_sizes"), st.plan(W(3), None, 17, targets=every).forward_stats(X)):
+        out["core/targets/" + part] = t.cpu()
+    for part, t in zip(("kg", "grad"), st.plan(W(3), None, 17, grad=True, targets=every).forward_grad(X)):
+        out["core/targets_grad/" + part] = t.cpu()
+    for part, t in zip(("kg", "grad"), st.plan(W(3), None, 17, grad=True, grad_rows="global").forward_grad(X)):
+        out["core/global_rows/" + part] = t.cpu()
+    for S in (9, 17):  # envelope split 2 and 3: wg_part, wg_gpart, tickets
+        w = W(S)
+        for part, t in zip(("kg", "pairs", "hull_sizes"), st.plan(w, 1, 17).forward_stats(X)):
+            out[f"core/S{S}/{part}"] = t.cpu()
+        for part, t in zip(("kg", "grad"), st.plan(w, 1, 17, grad=True).forward_grad(X)):
+            out[f"core/S{S}/grad_{part}"] = t.cpu()
+    # N + 1 > 64 * 33: streaming, no intercept scratch
+    wide = DeviceGPState(ModelListGPState(*plain), rnd(2112, d), dev)
+    out["core/N2112/kg"] = wide.plan(W(3), None, 3).forward(X[:3]).cpu()
+    # 32 batches of 16: the K(x, X) fill by candidate count, with its kx section
+    Xb, kg = rnd(512, d).to(dev), torch.empty(512, dtype=torch.double, device=dev)
+    DeviceGPState(ModelListGPState(*plain), rnd(20, d), dev).plan(W(3), None, 512).forward_batches_into(Xb, kg, 16)
+    out["core/batches/kg"] = kg.cpu()
+
+
 if len(sys.argv) > 2 and sys.argv[1] == "--dump":
     sys.path[:0] = [REPO, os.path.join(REPO, "decoupled-kg_amd")]
     import torch
@@ -95,8 +163,11 @@ if len(sys.argv) > 2 and sys.argv[1] == "--dump":
     from dkg_amd.synthetic import WORKLOADS, make_problem
 
     out = {}
-    dump_acquisition(out)
-    for name in () if "--acq-only" in sys.argv else ("small", "parity6d", "headline", "headline_nd", "stress"):
+    dump_core(out)
+    if "--core-only" not in sys.argv:
+        dump_acquisition(out)
+    only = "--acq-only" in sys.argv or "--core-only" in sys.argv
+    for name in () if only else ("small", "parity6d", "headline", "headline_nd", "stress"):
         w = WORKLOADS[name]
         model, D, X, W = make_problem(w)
         for target in (None, 1):
@@ -113,7 +184,7 @@ if len(sys.argv) > 2 and sys.argv[1] == "--dump":
 
 import torch  # noqa: E402
 
-flags = [a for a in sys.argv[3:] if a == "--acq-only"]
+flags = [a for a in sys.argv[3:] if a in ("--acq-only", "--core-only")]
 res = []
 for i, lib in enumerate(sys.argv[1:3]):
     path = f"/tmp/ab_{i}.pt"
@@ -122,7 +193,7 @@ for i, lib in enumerate(sys.argv[1:3]):
                    env=dict(os.environ, DKG_LIB=lib))
     res.append(torch.load(path))
 bad, table = 0, {}
-bits = lambda t: t.contiguous().view(torch.int64) if t.dtype == torch.double else t  # noqa: E731
+bits = lambda t: t.contiguous().view(torch.int64) if t.dtype == torch.double and t.dim() else t  # noqa: E731
 assert sorted(res[0]) == sorted(res[1])
 for k in res[0]:
     a, b = res[0][k], res[1][k]
