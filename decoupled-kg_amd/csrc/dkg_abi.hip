@@ -652,6 +652,126 @@ int dkg_append_observation(const dkg_output* o, int d, const double* L, const do
   return DKG_OK;
 }
 
+// Workspace of dkg_append_rows, walked once: the status words side by side (one copy back), the job descriptors
+// (one copy in), then each job's kx, bx, wp, kd and ch (RowsJob).  Returns the total; given `out` it fills the
+// descriptors' workspace pointers (offsets from `work`).
+static size_t carve_rows(const dkg_append_job* jobs, int J, void* work = nullptr, RowsJob* out = nullptr,
+                         size_t* desc_off = nullptr) {
+  Carve c;
+  c.take((size_t)J * sizeof(int));
+  const size_t desc = c.take((size_t)J * sizeof(RowsJob));
+  if (desc_off) *desc_off = desc;
+  for (int j = 0; j < J; ++j) {
+    const size_t n = jobs[j].o->n, np = pad16((int)n), K1 = jobs[j].K + 1;
+    const size_t kx = c.take(K1 * np * sizeof(double)), bx = c.take(K1 * np * sizeof(double));
+    const size_t wp = c.take((n + ROWS_CHUNK - 1) / ROWS_CHUNK * K1 * np * sizeof(double));
+    const size_t kd = c.take((size_t)jobs[j].K * pad16(jobs[j].N) * sizeof(double));
+    const size_t ch = c.take(ROWS_CH_DOUBLES * sizeof(double));
+    if (!out) continue;
+    out[j].kx = at<double>(work, kx);
+    out[j].bx = at<double>(work, bx);
+    out[j].wp = at<double>(work, wp);
+    out[j].kd = at<double>(work, kd);
+    out[j].ch = at<double>(work, ch);
+  }
+  return c.total();
+}
+
+// The sizes of one job (shared by the workspace query, which answers 0, and the call, which reports).
+static int check_rows_sizes(const dkg_append_job& b, int j) {
+  if (!b.o) return failf(DKG_ERR_ARG, "job %d: o is NULL", j);
+  if (b.o->n < 1) return failf(DKG_ERR_ARG, "job %d: n=%d training points", j, b.o->n);
+  if (b.K < 1) return failf(DKG_ERR_ARG, "job %d: K=%d new rows", j, b.K);
+  if (b.K > DKG_APPEND_MAX_ROWS)
+    return failf(DKG_ERR_UNSUPPORTED, "job %d: K=%d new rows (supported 1..%d)", j, b.K, DKG_APPEND_MAX_ROWS);
+  if (b.o->n > 1024 || pad16(b.o->n + b.K) > 1024)
+    return failf(DKG_ERR_UNSUPPORTED, "job %d: n=%d > 1024 training points", j, b.o->n + b.K);
+  if (b.N < 0) return failf(DKG_ERR_ARG, "job %d: N=%d discretisation points", j, b.N);
+  if (b.N > (1 << 22))
+    return failf(DKG_ERR_UNSUPPORTED, "job %d: N=%d discretisation points (supported <= %d)", j, b.N, 1 << 22);
+  return DKG_OK;
+}
+
+static int check_rows_count(const dkg_append_job* jobs, int J, int d) {
+  if (!jobs) return failf(DKG_ERR_ARG, "jobs is NULL");
+  if (J < 1) return failf(DKG_ERR_ARG, "J=%d jobs", J);
+  if (J > DKG_APPEND_MAX_JOBS) return failf(DKG_ERR_UNSUPPORTED, "J=%d jobs (supported 1..%d)", J, DKG_APPEND_MAX_JOBS);
+  if (d < 1 || d > DKG_MAX_DIM) return failf(DKG_ERR_UNSUPPORTED, "d=%d (supported 1..%d)", d, DKG_MAX_DIM);
+  return DKG_OK;
+}
+
+size_t dkg_append_rows_workspace(const dkg_append_job* jobs, int J, int d) {
+  if (check_rows_count(jobs, J, d)) return 0;
+  for (int j = 0; j < J; ++j)
+    if (check_rows_sizes(jobs[j], j)) return 0;
+  return carve_rows(jobs, J);
+}
+
+int dkg_append_rows(const dkg_append_job* jobs, int J, int d, int32_t* info, void* work, size_t work_bytes,
+                    void* stream) {
+  int st = check_rows_count(jobs, J, d);
+  if (st) return st;
+  if (!info) return failf(DKG_ERR_ARG, "info is NULL");
+  int nmax = 0, Kmax = 0, Nmax = 0;
+  for (int j = 0; j < J; ++j) {
+    const dkg_append_job& b = jobs[j];
+    if ((st = check_rows_sizes(b, j))) return st;
+    if ((st = check_outputs(b.o, 1, d))) return failf(st, "job %d: %s", j, std::string(dkg_last_error()).c_str());
+    if (!b.L || !b.Linv || !b.train_x || !b.train_y || !b.L_new || !b.Linv_new || !b.alpha_new || !b.root_frag_new)
+      return failf(DKG_ERR_ARG, "job %d: NULL pointer", j);
+    if (b.N > 0 && (!b.disc || !b.o->disc_frag || !b.disc_frag_new || !b.disc_mean_new))
+      return failf(DKG_ERR_ARG, "job %d: N=%d with a NULL discretisation pointer", j, b.N);
+    if (!(b.jitter >= 0.0)) return failf(DKG_ERR_ARG, "job %d: jitter=%g", j, b.jitter);
+    nmax = std::max(nmax, (int)b.o->n);
+    Kmax = std::max(Kmax, (int)b.K);
+    Nmax = std::max(Nmax, (int)b.N);
+  }
+  if (!work) return failf(DKG_ERR_ARG, "work is NULL");
+  const size_t need = carve_rows(jobs, J);
+  if (work_bytes < need) return failf(DKG_ERR_WORKSPACE, "workspace %zu bytes < required %zu", work_bytes, need);
+  hipStream_t s = (hipStream_t)stream;
+  std::vector<RowsJob> desc(J);
+  size_t desc_off = 0;
+  carve_rows(jobs, J, work, desc.data(), &desc_off);
+  for (int j = 0; j < J; ++j) {
+    const dkg_append_job& b = jobs[j];
+    RowsJob& a = desc[j];
+    a.o = *b.o;
+    a.L = b.L;
+    a.M = b.Linv;
+    a.xt = b.train_x;
+    a.y = b.train_y;
+    a.disc = b.disc;
+    a.diag = b.o->noise + b.jitter;  // as the old factorisation's kernel matrix took it
+    a.Ln = b.L_new;
+    a.Mn = b.Linv_new;
+    a.alpha = b.alpha_new;
+    a.rf = b.root_frag_new;
+    a.qn = b.disc_frag_new;
+    a.mean = b.disc_mean_new;
+    a.N = b.N;
+    a.K = b.K;
+  }
+  int* d_info = static_cast<int*>(work);
+  RowsJob* d_jobs = at<RowsJob>(work, desc_off);
+  for (int j = 0; j < J; ++j) info[j] = -1;
+  if ((st = hip_status(hipMemcpyAsync(d_jobs, desc.data(), (size_t)J * sizeof(RowsJob), hipMemcpyHostToDevice, s),
+                       "hipMemcpyAsync")) ||
+      (st = hip_status(hipMemsetAsync(d_info, 0xff, (size_t)J * sizeof(int), s), "hipMemsetAsync")) ||
+      (st = hip_status(launch_append_rows(d_jobs, J, d, nmax, Kmax, Nmax, d_info, s), "append_rows")) ||
+      (st = hip_status(hipMemcpyAsync(info, d_info, (size_t)J * sizeof(int), hipMemcpyDeviceToHost, s),
+                       "hipMemcpyAsync")) ||
+      (st = hip_status(hipStreamSynchronize(s), "hipStreamSynchronize")))
+    return st;
+  int bad = 0, first = -1;
+  for (int j = 0; j < J; ++j)
+    if (info[j] != 0 && bad++ == 0) first = j;
+  if (bad)
+    return failf(DKG_ERR_NOT_PD, "covariance not positive definite with the appended rows: %d of %d jobs, the first "
+                 "job %d (pivot %d)", bad, J, first, info[first]);
+  return DKG_OK;
+}
+
 size_t dkg_forward_workspace(const dkg_output* outs, int m, int N, int B, int S) {
   if (!outs || m < 1 || m > DKG_MAX_OUTPUTS) return 0;
   return carve_plan(outs, m, N, B, S, 0, 0, 1) + plan_slot_bytes() + 256;

@@ -182,6 +182,30 @@ struct AppendArgs {
 constexpr size_t APPEND_WS_LAM = 64, APPEND_WS_L = 256, APPEND_WS_BETA = 256 + 8192, APPEND_WS_BYTES = 256 + 16384;
 // The copy, solve, pack and discretisation launches of one append (root_frag: the new R^T, from Mn).
 hipError_t launch_append(const AppendArgs& a, double* root_frag, hipStream_t s);
+// A block of K rows appended to many states at once (dkg_append.hip, dkg_append_rows): one job per (state, output),
+// its descriptor resident in the workspace; every launch carries all jobs (one grid dimension over them).
+constexpr int ROWS_MAX = DKG_APPEND_MAX_ROWS;  // K <= 32; the kernels carry K + 1 vectors (the rows, then r' / beta)
+constexpr int ROWS_CHUNK = 128;                // rows of M per workgroup of the W = B M stage
+constexpr int ROWS_CH_DOUBLES = ROWS_MAX * ROWS_MAX + 2 * ROWS_MAX;  // C^{-1} [32][32], beta2 [32], gamma [32]
+struct RowsJob {
+  dkg_output o;            // the old output: n, kernel, hyperparameters, inv_lengthscale, disc_frag
+  const double *L, *M;     // old L and L^{-1}, row-major n x n
+  const double* xt;        // new train_x, (n + K) x d, the old rows first
+  const double* y;         // new targets, n + K
+  const double* disc;      // [N x d]
+  double diag;             // noise + the old factorisation's jitter
+  double *Ln, *Mn;         // new L and L^{-1}, (n + K) x (n + K)
+  double *alpha, *rf;      // [pad16(n + K)], fragment-packed M' [pad16(n + K)^2]
+  double *qn, *mean;       // new disc_frag N_pad x pad16(n + K), new disc_mean [N_pad]
+  // workspace, np = pad16(n): kx [K + 1][np] = s kappa(X2, X), then r'[0..n);  bx [K + 1][np] = B, then beta;
+  // wp [ceil(n / ROWS_CHUNK)][K + 1][np] = the row chunks' partial sums of B M, then of M^T beta;
+  // kd [K][N_pad] = s kappa(X2, D);  ch [ROWS_CH_DOUBLES]
+  double *kx, *bx, *wp, *kd, *ch;
+  int N, K;
+};
+// The launches of one dkg_append_rows: nmax, Kmax and Nmax are the largest n, K and N of the jobs (grid sizes).
+hipError_t launch_append_rows(const RowsJob* jobs, int J, int d, int nmax, int Kmax, int Nmax, int* info,
+                              hipStream_t s);
 // Marginal log-likelihood and its gradient (dkg_mll.hip, dkg_mll_value_grad): after the factorisation, inverse
 // and alpha of every output.  part: [mll_tiles(n)][MLL_NP] tile partials; out: [MLL_OUT] = value, then the
 // gradient [c, l_1 .. l_d, s, noise].

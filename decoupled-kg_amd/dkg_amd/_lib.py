@@ -81,8 +81,22 @@ class DkgRffPaths(ctypes.Structure):
                 ("bias", c_void_p), ("coef", c_void_p), ("offset", c_void_p)]
 
 
+DKG_APPEND_MAX_ROWS, DKG_APPEND_MAX_JOBS = 32, 512  # include/dkg.h: the limits of dkg_append_rows
+
+
+class DkgAppendJob(ctypes.Structure):
+    """``struct dkg_append_job`` (include/dkg.h): one (state, output) of a ``dkg_append_rows`` call."""
+
+    _fields_ = [("o", POINTER(DkgOutput)), ("L", c_void_p), ("Linv", c_void_p), ("disc", c_void_p), ("N", c_int32),
+                ("K", c_int32), ("train_x", c_void_p), ("train_y", c_void_p), ("jitter", c_double),
+                ("L_new", c_void_p), ("Linv_new", c_void_p), ("alpha_new", c_void_p), ("root_frag_new", c_void_p),
+                ("disc_frag_new", c_void_p), ("disc_mean_new", c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol include/dkg.h declares.
 SIGNATURES = {
+    "dkg_append_rows_workspace": (c_size_t, [POINTER(DkgAppendJob), c_int, c_int]),
+    "dkg_append_rows": (c_int, [POINTER(DkgAppendJob), c_int, c_int, POINTER(c_int32), c_void_p, c_size_t, c_void_p]),
     "dkg_rff_workspace": (c_size_t, [c_int, c_int]),
     "dkg_rff_weights": (c_int, [POINTER(DkgOutput), c_int, c_int, POINTER(c_void_p), c_void_p, c_void_p, c_void_p,
                                 c_void_p, c_int, POINTER(DkgRffPaths), c_void_p, c_size_t, POINTER(c_double),

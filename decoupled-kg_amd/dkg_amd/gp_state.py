@@ -179,6 +179,100 @@ def append_observation(cache: OutputCache, D: torch.Tensor, x, train_y) -> Outpu
     return OutputCache(new_st, cache.inv_ls, X, alpha, root_frag, disc_frag, disc_mean, L, cache.jitter, o, linv)
 
 
+def append_observations(caches, D: torch.Tensor, X_new, train_y, check: bool = True):
+    """A block of rows appended to each of several fitted outputs in one batched update (``dkg_append_rows``):
+    job ``j`` turns ``caches[j]``, the caches of ``(X, y)``, into those of ``([X; X_new[j]], train_y[j])`` --
+    exact-GP conditioning on ``K_j = X_new[j].shape[0]`` new rows, no refactorisation.  ``caches``, ``X_new``
+    (``[K_j, d]`` each, ``1 <= K_j <= 32``) and ``train_y`` (all ``n_j + K_j`` targets each, model space) are
+    sequences of equal length; the same cache may appear in several jobs.  ``D`` is the device discretisation
+    every cache was built over, or an empty ``[0, d]`` tensor.  One host-to-device copy carries all new rows
+    and targets, one C call runs all jobs, and ``alpha`` is formed from all targets of a job (the old ones
+    may change).  Out of place.  Returns the new ``OutputCache`` list.
+
+    Raises ``NotPSDError`` naming the jobs whose grown covariance is not positive definite under the old
+    jitter (``.jobs``: their indices; ``.caches``: the list with ``None`` at those jobs), and
+    ``UnsupportedError`` beyond 32 rows, 512 jobs or 1024 training points.  ``check=False`` returns the list
+    with ``None`` at the failed jobs instead of raising."""
+    from .errors import NotPSDError
+
+    lib = _lib.load()
+    caches, X_new, train_y = list(caches), list(X_new), list(train_y)
+    J = len(caches)
+    if not (J == len(X_new) == len(train_y)):
+        raise ValueError(f"{J} caches, {len(X_new)} row blocks and {len(train_y)} target vectors")
+    if J == 0:
+        return []
+    if J > _lib.DKG_APPEND_MAX_JOBS:
+        raise UnsupportedError(f"{J} jobs > {_lib.DKG_APPEND_MAX_JOBS} per call is not supported")
+    dev = D.device
+    N, d = D.shape
+    host, shapes = [], []
+    for j, (c, x, y) in enumerate(zip(caches, X_new, train_y)):
+        n = c.train_x.shape[0]
+        xh = torch.as_tensor(x, dtype=torch.double).detach().cpu().reshape(-1, d)
+        yh = torch.as_tensor(y, dtype=torch.double).detach().cpu().reshape(-1)
+        K = xh.shape[0]
+        if K < 1:
+            raise ValueError(f"job {j}: no new rows")
+        if K > _lib.DKG_APPEND_MAX_ROWS:
+            raise UnsupportedError(f"job {j}: K={K} new rows > {_lib.DKG_APPEND_MAX_ROWS} per call is not supported")
+        if _pad16(n + K) > 1024:
+            raise UnsupportedError(f"job {j}: n={n + K} training points > 1024 per output is not supported")
+        if yh.numel() != n + K:
+            raise ValueError(f"job {j}: train_y has {yh.numel()} entries for {n + K} training points")
+        host += [xh.reshape(-1), yh]
+        shapes.append((n, K, xh, yh))
+    flat = torch.cat(host).to(dev)  # every job's new rows and targets in one host-to-device copy
+    jobs = (_lib.DkgAppendJob * J)()
+    parts, off = [], 0
+    for j, (c, (n, K, xh, yh)) in enumerate(zip(caches, shapes)):
+        X = torch.cat([c.train_x, flat[off:off + K * d].view(K, d)])
+        y = flat[off + K * d:off + K * d + n + K]
+        off += K * d + n + K
+        n1 = n + K
+        L = torch.empty(n1, n1, dtype=torch.double, device=dev)
+        linv = torch.empty(n1, n1, dtype=torch.double, device=dev)
+        alpha = torch.empty(_pad16(n1), dtype=torch.double, device=dev)
+        root_frag = torch.empty(lib.dkg_frag_elems(n1, n1), dtype=torch.double, device=dev)
+        disc_frag = torch.empty(max(1, lib.dkg_frag_elems(N, n1)), dtype=torch.double, device=dev)
+        disc_mean = torch.empty(max(16, _pad16(N)), dtype=torch.double, device=dev)
+        parts.append((X, y, L, linv, alpha, root_frag, disc_frag, disc_mean))
+        b = jobs[j]
+        b.o = ctypes.pointer(c.struct)
+        b.L, b.Linv, b.disc, b.N, b.K = _lib.ptr(c.L), _lib.ptr(c.Linv), _lib.ptr(D) if N else None, N, K
+        b.train_x, b.train_y, b.jitter = _lib.ptr(X), _lib.ptr(y), float(c.jitter)
+        b.L_new, b.Linv_new, b.alpha_new, b.root_frag_new = (_lib.ptr(L), _lib.ptr(linv), _lib.ptr(alpha),
+                                                             _lib.ptr(root_frag))
+        b.disc_frag_new, b.disc_mean_new = _lib.ptr(disc_frag), _lib.ptr(disc_mean)
+    work = torch.empty(lib.dkg_append_rows_workspace(jobs, J, d), dtype=torch.uint8, device=dev)
+    info = (ctypes.c_int32 * J)()
+    status = lib.dkg_append_rows(jobs, J, d, info, _lib.ptr(work), work.numel(), current_stream_ptr(dev))
+    if status != _lib.DKG_ERR_NOT_PD:
+        _lib.check(status, "dkg_append_rows")
+    out = []
+    for j, (c, (n, K, xh, yh)) in enumerate(zip(caches, shapes)):
+        if info[j] != 0:
+            out.append(None)
+            continue
+        st = c.state
+        X, y, L, linv, alpha, root_frag, disc_frag, disc_mean = parts[j]
+        new_st = SingleTaskGPState(torch.cat([st.train_x, xh]), yh.clone(), st.lengthscale, st.outputscale, st.noise,
+                                   st.mean_constant, st.kernel, st.nu, st.y_mean, st.y_std)
+        o = _base_struct(new_st, c.inv_ls, X)
+        o.alpha = _lib.ptr(alpha)
+        o.root_frag = _lib.ptr(root_frag)
+        o.disc_frag = _lib.ptr(disc_frag)
+        o.disc_mean = _lib.ptr(disc_mean)
+        out.append(OutputCache(new_st, c.inv_ls, X, alpha, root_frag, disc_frag, disc_mean, L, c.jitter, o, linv))
+    failed = [j for j in range(J) if info[j] != 0]
+    if failed and check:
+        err = NotPSDError(f"dkg_append_rows: covariance not positive definite with the appended rows in jobs {failed} "
+                          f"of {J} (pivots {[int(info[j]) for j in failed]}); rebuild those with prepare_outputs")
+        err.jobs, err.caches = failed, out
+        raise err
+    return out
+
+
 # The opt-in incremental path of discretekg.shared_state (off by default: nothing that exists changes bits)
 # and the counters of how the shared device states were made.
 _INCREMENTAL = False
@@ -308,6 +402,26 @@ class DeviceGPState:
             train_y = torch.cat([old.state.train_y, torch.as_tensor(y, dtype=torch.double).detach().cpu().reshape(1)])
         with torch.cuda.device(self.device):
             new = append_observation(old, self.D, x, train_y)
+        return self._with_output(i, new)
+
+    def with_observations(self, output_ix: int, X, y=None, train_y=None) -> "DeviceGPState":
+        """``with_observation`` for a block of rows ``X`` (``[K, d]``, ``1 <= K <= 32``) in one batched update
+        (``append_observations``).  Give the K new targets ``y`` (appended to the output's targets) or all
+        n + K targets ``train_y``.  Raises ``NotPSDError`` / ``UnsupportedError`` as ``append_observations``."""
+        if not 0 <= int(output_ix) < self.m:
+            raise IndexError(f"output index {output_ix} out of range for {self.m} outputs")
+        if (y is None) == (train_y is None):
+            raise ValueError("give exactly one of y (the K new targets) and train_y (all n + K targets)")
+        i = int(output_ix)
+        old = self.outputs[i]
+        if train_y is None:
+            train_y = torch.cat([old.state.train_y, torch.as_tensor(y, dtype=torch.double).detach().cpu().reshape(-1)])
+        with torch.cuda.device(self.device):
+            (new,) = append_observations([old], self.D, [X], [train_y])
+        return self._with_output(i, new)
+
+    def _with_output(self, i: int, new: OutputCache) -> "DeviceGPState":
+        """A state that shares every output's caches with this one but output ``i``'s."""
         st = object.__new__(DeviceGPState)
         st.device = self.device
         st.D, st.N, st.d, st.m = self.D, self.N, self.d, self.m

@@ -13,8 +13,9 @@ Same surface as the reference's ``decoupledbo.modules.acquisition.joint_entropy_
 The model conditioned on each sampled Pareto set (``condition_on_observations`` with observation noise,
 ``:365-376``) is built once at construction as a fitted state of its own: the sample's rows appended to every
 output's training data, hyperparameters, noise and Standardize statistics unchanged, factorised by the full
-preparation (``gp_state.prepare_outputs``, the oracle's jitter policy).  Every evaluation is then two HIP kernel
-launches through the C ABI (``include/dkg.h`` ``dkg_jes_*``).  There is no CPU fallback.
+preparation (``gp_state.prepare_outputs``, the oracle's jitter policy), or with ``conditioning="append"`` from the
+model's own caches by one batched block update (``gp_state.append_observations``).  Every evaluation is then two
+HIP kernel launches through the C ABI (``include/dkg.h`` ``dkg_jes_*``).  There is no CPU fallback.
 """
 
 from __future__ import annotations
@@ -33,6 +34,9 @@ from .model import ModelListGPState, SingleTaskGPState
 NEG_INF = -1e10  # the reference point of the box decompositions (BoTorch's compute_sample_box_decomposition)
 ESTIMATION_TYPES = ["0", "LB", "LB2", "MC"]
 SUPPORTED_ESTIMATION_TYPES = ("LB", "LB2")
+# how the conditioned states are built: the full preparation of every state (the default: the oracle's jitter policy
+# and the bits every result has had), or one batched block update of state 0's caches (gp_state.append_observations)
+CONDITIONING = ("refactorise", "append")
 
 
 def _nondominated_sorted_2d(pf: Tensor) -> Tensor:
@@ -146,7 +150,10 @@ class qLowerBoundMultiObjectiveJointEntropySearch(_Base):
 
     def __init__(self, model, pareto_sets: List[Tensor], pareto_fronts: List[Tensor], hypercell_bounds: Tensor,
                  X_pending: Optional[Tensor] = None, estimation_type: str = "LB", num_samples: int = 64,
-                 target_output_ix: Optional[int] = None, device=None, **kwargs) -> None:
+                 target_output_ix: Optional[int] = None, device=None, conditioning: str = "refactorise",
+                 **kwargs) -> None:
+        if conditioning not in CONDITIONING:
+            raise ValueError(f"conditioning must be one of {CONDITIONING}, got {conditioning!r}")
         if _HAVE_BOTORCH:  # pragma: no cover
             super().__init__(model=model)
         else:
@@ -224,11 +231,42 @@ class qLowerBoundMultiObjectiveJointEntropySearch(_Base):
         # discretisation, one call per state
         states = [state] + conditioned_states(state, pareto_sets, pareto_fronts)
         empty = torch.empty(0, d, dtype=torch.double, device=dev)
+        self.conditioning = conditioning
+        self.append_fallbacks = 0  # "append": the conditioned outputs that took the full preparation instead
         with torch.cuda.device(dev):
-            self._caches = [gp_state.prepare_outputs(s.models, empty) for s in states]
+            if conditioning == "refactorise":
+                self._caches = [gp_state.prepare_outputs(s.models, empty) for s in states]
+            else:
+                self._caches = self._append_caches(states, empty)
         self._structs = (_lib.DkgOutput * ((P + 1) * m))(*[c.struct for cs in self._caches for c in cs])
         self._bounds = hypercell_bounds.detach().to(dev, torch.double).contiguous()
         self._plan = None
+
+    def _append_caches(self, states: List[ModelListGPState], empty: Tensor):
+        """``conditioning="append"``: state 0 by the full preparation, the conditioned states from its caches by
+        one batched block update over the P m (sample, output) jobs (``gp_state.append_observations``).  A job
+        whose base output was factorised with jitter, or whose update is not positive definite, takes the full
+        preparation instead (the oracle's jitter policy), and is counted in ``append_fallbacks``."""
+        base = gp_state.prepare_outputs(states[0].models, empty)
+        m = len(base)
+        # (a sample of more than DKG_APPEND_MAX_ROWS points is beyond the block update: the full preparation too)
+        jobs = [(p, i) for p in range(1, len(states)) for i in range(m) if base[i].jitter == 0.0
+                and 1 <= states[p].models[i].num_train - base[i].train_x.shape[0] <= _lib.DKG_APPEND_MAX_ROWS]
+        new = gp_state.append_observations(
+            [base[i] for _, i in jobs], empty,
+            [states[p].models[i].train_x[base[i].train_x.shape[0]:] for p, i in jobs],
+            [states[p].models[i].train_y for p, i in jobs], check=False)
+        done = {job: cache for job, cache in zip(jobs, new) if cache is not None}
+        caches = [base]
+        for p in range(1, len(states)):
+            row = []
+            for i in range(m):
+                if (p, i) not in done:
+                    self.append_fallbacks += 1
+                    done[(p, i)] = gp_state.prepare_output(states[p].models[i], empty)
+                row.append(done[(p, i)])
+            caches.append(row)
+        return caches
 
     def set_X_pending(self, X_pending: Optional[Tensor] = None) -> None:
         if X_pending is not None:

@@ -362,7 +362,7 @@ class JesOptimisationSpec:
     def __init__(self, estimation_type: str, num_pareto_samples: int, num_pareto_points: int, num_restarts: int,
                  raw_samples: int, batch_limit: int, max_iter: int, pareto_sampler: Callable, device=None,
                  seed: Optional[int] = None, acq_factory: Optional[Callable] = None,
-                 hypercell_bounds_fn: Optional[Callable] = None):
+                 hypercell_bounds_fn: Optional[Callable] = None, conditioning: str = "refactorise"):
         if not callable(pareto_sampler):
             raise TypeError("pareto_sampler(model, bounds, num_samples, target_num_points) must be callable")
         self.estimation_type = estimation_type
@@ -379,12 +379,15 @@ class JesOptimisationSpec:
         # acquisition: None builds the device acquisition (tests inject the CPU restatement to compare runs)
         self.acq_factory = acq_factory
         self.hypercell_bounds_fn = hypercell_bounds_fn
+        # how the device acquisition builds its conditioned states ("refactorise" / "append", dkg_amd.jes)
+        self.conditioning = conditioning
 
     @classmethod
     def with_device_sampler(cls, estimation_type: str, num_pareto_samples: int, num_pareto_points: int,
                             num_restarts: int, raw_samples: int, batch_limit: int, max_iter: int, device=None,
                             seed: Optional[int] = None, acq_factory: Optional[Callable] = None,
-                            hypercell_bounds_fn: Optional[Callable] = None, **sampler_kwargs) -> "JesOptimisationSpec":
+                            hypercell_bounds_fn: Optional[Callable] = None, conditioning: str = "refactorise",
+                            **sampler_kwargs) -> "JesOptimisationSpec":
         """A spec whose Pareto samples come from the device sampler
         (``jes_pareto.sample_discrete_pareto_optimal_points``: random-Fourier-feature paths, NSGA-II and pruning,
         ``jes_sample_pareto.py:48-98``), as the reference's spec does at
@@ -399,7 +402,7 @@ class JesOptimisationSpec:
 
         return cls(estimation_type, num_pareto_samples, num_pareto_points, num_restarts, raw_samples, batch_limit,
                    max_iter, pareto_sampler=sampler, device=device, seed=seed, acq_factory=acq_factory,
-                   hypercell_bounds_fn=hypercell_bounds_fn)
+                   hypercell_bounds_fn=hypercell_bounds_fn, conditioning=conditioning)
 
     def _options(self) -> Dict:
         opts = {"batch_limit": self.batch_limit, "maxiter": self.max_iter}
@@ -430,7 +433,8 @@ class JesOptimisationSpec:
             return self.acq_factory(model, pareto_sets, pareto_fronts, hypercell_bounds, self.estimation_type, target)
         return qLowerBoundMultiObjectiveJointEntropySearch(model, pareto_sets, pareto_fronts, hypercell_bounds,
                                                            estimation_type=self.estimation_type,
-                                                           target_output_ix=target, device=self.device)
+                                                           target_output_ix=target, device=self.device,
+                                                           conditioning=self.conditioning)
 
     def optimize_for_single_objective(self, model, costs: Union[Tensor, Sequence], input_dim: int,
                                       **_unused_kwargs) -> Tuple[Tensor, int, Tensor]:

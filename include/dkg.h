@@ -42,7 +42,8 @@ extern "C" {
 #define DKG_ABI_VERSION 9  /* 9: dkg_append_observation; 8: dkg_plan_forward_batches, dkg_plan_time_stage_batches */
 /* Added under 9 since (new symbols only; nothing that existed changed): dkg_mll_*, dkg_posterior_mean, dkg_pareto_*,
  * dkg_jes_*, dkg_rff_workspace, dkg_rff_weights, dkg_rff_eval, dkg_debug_rff_gram, dkg_pareto_paths_workspace,
- * dkg_pareto_nsga2_paths, dkg_pareto_prune, dkg_hvkg_*, dkg_hypervolume, dkg_dominated_boxes*, dkg_hypervolume_front*. */
+ * dkg_pareto_nsga2_paths, dkg_pareto_prune, dkg_hvkg_*, dkg_hypervolume, dkg_dominated_boxes*, dkg_hypervolume_front*,
+ * dkg_append_rows*. */
 #define DKG_MAX_OUTPUTS 8   /* outputs (objectives) per model list */
 #define DKG_MAX_DIM 16      /* input dimension d */
 
@@ -165,6 +166,49 @@ int dkg_append_observation(const dkg_output* o, int d, const double* L, const do
                            const double* train_x, const double* train_y, double jitter, double* L_new,
                            double* Linv_new, double* alpha_new, double* root_frag_new, double* disc_frag_new,
                            double* disc_mean_new, void* work, size_t work_bytes, void* stream);
+
+/* A block of K observations appended to each of J fitted states in one batched update: exact-GP conditioning on
+ * new rows (BoTorch's condition_on_observations) without refactorising, every launch carrying all jobs.  One
+ * job, with M = L^{-1}, X2 the K new rows, r' = y' - c, j the old factorisation's jitter:
+ *   B  = s kappa(X2, X) M^T  [K x n],   beta = M r'[0..n)
+ *   S  = s kappa(X2, X2) + (noise + j) I - B B^T,  C = chol(S)   (a pivot <= 0 or not finite: not positive definite)
+ *   W  = B M,   L' = [[L, 0], [B, C]],   M' = [[M, 0], [-C^{-1} W, C^{-1}]]
+ *   beta2 = C^{-1} (r'[n..) - B beta),  gamma = C^{-T} beta2,  alpha' = M'^T M' r' = [M^T beta - W^T gamma ; gamma]
+ *   Q_D' = [Q_D, (s kappa(D, X2) - Q_D B^T) C^{-T}],  mu_D' = c + Q_D beta + Q_D'[:, n..) beta2
+ * alpha' is always formed from all n + K targets, as dkg_append_observation forms it: the old targets may change.
+ *   o, L, Linv, disc, N, jitter : as dkg_append_observation reads them (o also passes dkg_cross_root's checks)
+ *   K       : new rows, 1..DKG_APPEND_MAX_ROWS, with n_pad(n + K) <= 1024
+ *   train_x : device [(n + K) x d], the old rows first;  train_y: device [n + K]
+ *   L_new, Linv_new [(n + K)^2], alpha_new [n_pad(n + K)], root_frag_new [n_pad(n + K)^2],
+ *   disc_frag_new [N_pad x n_pad(n + K)], disc_mean_new [N_pad]: device, written; padding exactly zero.
+ * Out of place; fp64; no atomics; every sum in a fixed order that depends on the job's own n, K and N alone, so a
+ * job's bits do not depend on the other jobs of the call or on its position among them.  The number of launches
+ * does not depend on J. */
+#define DKG_APPEND_MAX_ROWS 32
+#define DKG_APPEND_MAX_JOBS 512   /* DKG_JES_MAX_SAMPLES x DKG_MAX_OUTPUTS */
+typedef struct dkg_append_job {
+  const dkg_output* o;               /* old state, as dkg_append_observation reads it */
+  const double *L, *Linv;            /* old, device [n x n] */
+  const double* disc; int32_t N;     /* NULL / 0: no discretisation */
+  int32_t K;
+  const double* train_x;             /* device [(n + K) x d], the old rows first */
+  const double* train_y;             /* device [n + K] */
+  double jitter;
+  double *L_new, *Linv_new, *alpha_new, *root_frag_new, *disc_frag_new, *disc_mean_new;
+} dkg_append_job;
+
+/* Bytes of device scratch dkg_append_rows needs for these jobs; 0 for NULL jobs, J outside
+ * 1..DKG_APPEND_MAX_JOBS, d outside 1..DKG_MAX_DIM, or a job with a NULL o, n < 1, K outside
+ * 1..DKG_APPEND_MAX_ROWS, n_pad(n + K) > 1024 or N < 0. */
+size_t dkg_append_rows_workspace(const dkg_append_job* jobs, int J, int d);
+
+/* Runs the J jobs.  info: host [J], receives 0 or, for a job that is not positive definite, the failing column
+ * + 1 (n + the failing pivot of S + 1); such a job's outputs are not to be used, the others' are complete.
+ * Synchronises `stream` once, for all status words.  DKG_OK when every job succeeded, DKG_ERR_NOT_PD when any
+ * failed; DKG_ERR_ARG for NULL pointers and bad sizes, DKG_ERR_UNSUPPORTED for K, J or n + K beyond the limits,
+ * DKG_ERR_WORKSPACE for a short workspace: the arguments are checked before any HIP call. */
+int dkg_append_rows(const dkg_append_job* jobs, int J, int d, int32_t* info, void* work, size_t work_bytes,
+                    void* stream);
 
 /* Bytes of device scratch dkg_mll_value_grad needs for m outputs of n[i] training points; 0 for a NULL n,
  * m outside 1..DKG_MAX_OUTPUTS or an n[i] outside 1..1024. */
