@@ -1129,6 +1129,16 @@ int dkg_debug_envelope_lds(int m, int N, int waves, int S, int d, int max_np, in
   return DKG_OK;
 }
 
+int dkg_debug_envelope_deal(int L, int nitems, int groups, int* item, int* member) {
+  if (!item || !member || nitems < 1 || groups < 1 ||
+      8ll * groups * (((long long)nitems + 7) / 8) > 0x7fffffffll || L < 0 || L >= xcd_group_size(nitems, groups)) {
+    failf(DKG_ERR_ARG, "dkg_debug_envelope_deal: L=%d nitems=%d groups=%d item=%s member=%s", L, nitems, groups,
+          item ? "set" : "NULL", member ? "set" : "NULL");
+    return -2;
+  }
+  return xcd_deal(L, nitems, groups, *item, *member) ? 1 : 0;
+}
+
 int dkg_debug_wave_ops(const double* in, double* out, void* stream) {
   if (!in || !out) return failf(DKG_ERR_ARG, "NULL pointer");
   return hip_status(launch_debug_wave(in, out, (hipStream_t)stream), "debug_wave_kernel");

@@ -523,6 +523,25 @@ __device__ __forceinline__ bool xcd_group(int L, int nblk, int groups, int& blk,
   return blk < nblk;
 }
 
+// xcd_group for launches whose work depends on the data (the envelope stage: a workgroup with a pair that fails
+// the flat test walks it, 2-3x a flat workgroup's time).  xcd_group runs item b on the XCD of launch residue
+// b % 8, and a candidate set with spatial order in its index (a Sobol sequence's index modulo 8 is a stratum;
+// grids; restarts kept in order) then puts its expensive items on a few XCDs, which finish last while the others
+// idle.  Same grid (xcd_group_size) and the members of one item still on consecutive ids of one XCD, but within
+// every aligned group of eight items q = item / 8 the residues rotate: launch residue L & 7 takes item
+// 8 q + ((L & 7) - q - q / 8) mod 8, so item b runs on residue (b + b / 8 + b / 64) mod 8 and over any aligned
+// 512 items every residue takes every (b % 8, (b / 8) % 8) once.  A fixed map cannot balance arbitrary data; it
+// keeps the index structure from lining up with the hardware's modulo 8.  False for the padding ids.
+#ifndef DKG_ENV_DEAL
+#define DKG_ENV_DEAL 1  // 0 (A/B builds, tools/build_variant.sh): xcd_group's order, for the per-XCD stamps of both
+#endif
+__host__ __device__ inline bool xcd_deal(int L, int nitems, int groups, int& item, int& member) {
+  const int r = L >> 3, q = r / groups;
+  member = r - q * groups;
+  item = 8 * q + (DKG_ENV_DEAL ? ((L & 7) - q - (q >> 3)) & 7 : L & 7);
+  return item < nitems;
+}
+
 // Block order of a launch over (column block bx < nbx, row block by < nby, output oi < m) whose workgroups
 // each read a row panel (by, oi) and a column panel (bx, oi): order 0 is xcd_group's (the outputs of one block
 // side by side, blocks dealt over the XCDs); orders 1 and 2 give every XCD a contiguous range of the task list

@@ -21,7 +21,27 @@ __device__ __forceinline__ unsigned long long* kst_slot(int dst, const Plan* P, 
   const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
   return (threadIdx.x == 0 && wg < KST_WG) ? P->kstamps + ((size_t)kid * KST_WG + wg) * 8 : nullptr;
 }
-#define KST_BEGIN(st)                                                  \
+// DKG_DEBUG_STAMPS=3: the envelope launch alone, two words per workgroup over the whole buffer (KST_WIDE
+// workgroups, enough for 32 headline batches): word 0 = s_memrealtime at start, word 1 = s_memrealtime at end
+// with the XCD the workgroup ran on (HW_REG_XCC_ID, bits 3:0) in bits 63:60.  tools/kstamps.py --xcd reads them.
+constexpr int KST_WIDE = 3 * KST_WG * 4;
+__device__ __forceinline__ unsigned long long* kst_wide(int dst, const Plan* P) {
+  if (dst != 3) return nullptr;
+  return (threadIdx.x == 0 && blockIdx.x < KST_WIDE) ? P->kstamps + 2 * (size_t)blockIdx.x : nullptr;
+}
+__device__ __forceinline__ void kst_wide_begin(int dst, const Plan* P) {
+  if (unsigned long long* wst = kst_wide(dst, P)) wst[0] = __builtin_amdgcn_s_memrealtime();
+}
+// Nothing of the stamp is live across the body: the slot is found again at the end.
+__device__ __forceinline__ void kst_wide_end(int dst, const Plan* P) {
+  if (dst != 3) return;
+  __syncthreads();  // dst is a kernel argument: workgroup-uniform; the end stamp covers every wave
+  if (unsigned long long* wst = kst_wide(dst, P)) {
+    const unsigned long long xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 0xf;  // HW_REG_XCC_ID[3:0]
+    wst[1] = (__builtin_amdgcn_s_memrealtime() & 0x0fffffffffffffffull) | (xcc << 60);
+  }
+}
+#define KST_BEGIN(st)                                               \
   do {                                                                 \
     if (st) {                                                          \
       (st)[0] = __builtin_amdgcn_s_memrealtime();                      \
@@ -2722,12 +2742,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(env_waves_p
                                                        int bpad, double* __restrict__ hout, int split) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   if (DKG_ABLATIONS && (__builtin_amdgcn_readfirstlane(P->debug_env) & 2)) return;  // ablation: empty envelope stage
-  // 1-D grid: the `split` workgroups of one candidate side by side on one XCD (xcd_group), so its line
-  // records come from HBM once and from that XCD's L2 for the others
+  // 1-D grid: the `split` workgroups of one candidate side by side on one XCD, so its line
+  // records come from HBM once and from that XCD's L2 for the others; the candidates dealt over the XCDs by
+  // xcd_deal, not xcd_group: the stage's work depends on the data
   int b, g;
-  if (!xcd_group(blockIdx.x, B, split, b, g)) return;
+  if (!xcd_deal(blockIdx.x, B, split, b, g)) return;
+  kst_wide_begin(dst, P);
   envelope_body<MAXL, M, GRAD, STREAM>(P, B, kg, pairs_out, dst, xnew, dkg, mu_all, cov_all, var_all, mux_all, wts,
                                        dupv, cov_stride, bpad, b, g, split, smem, kst_slot(dst, P, 2), nullptr, hout);
+  kst_wide_end(dst, P);
 }
 
 // The envelope stage of a plan of ntgt > 1 targets: ntgt * split workgroups per candidate, side by side on one
@@ -2748,13 +2771,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(env_waves_p
   extern __shared__ __attribute__((aligned(16))) double smem[];
   if (DKG_ABLATIONS && (__builtin_amdgcn_readfirstlane(P->debug_env) & 2)) return;  // ablation: empty envelope stage
   int b, g;
-  if (!xcd_group(blockIdx.x, B, split * ntgt, b, g)) return;
+  if (!xcd_deal(blockIdx.x, B, split * ntgt, b, g)) return;
+  kst_wide_begin(dst, P);
   const int tau = g / split;
   g -= tau * split;
   envelope_body<MAXL, M, GRAD, STREAM, false, true>(P, B, kg, pairs_out, dst, xnew, dkg, mu_all, cov_all, var_all,
                                                     mux_all, wts, dupv, cov_stride, bpad, b, g, split, smem,
                                                     kst_slot(dst, P, 2), nullptr, hout, tau, ntgt,
                                                     target_of(tpack, tau));
+  kst_wide_end(dst, P);
 }
 
 // The streaming value+gradient envelope with global rows (envelope_body GROWS; DKG_PLAN_GRAD_GLOBAL_ROWS): kernels of
@@ -2773,10 +2798,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(env_waves_p
   extern __shared__ __attribute__((aligned(16))) double smem[];
   if (DKG_ABLATIONS && (__builtin_amdgcn_readfirstlane(P->debug_env) & 2)) return;  // ablation: empty envelope stage
   int b, g;
-  if (!xcd_group(blockIdx.x, B, split, b, g)) return;
+  if (!xcd_deal(blockIdx.x, B, split, b, g)) return;
+  kst_wide_begin(dst, P);
   envelope_body<STREAM_CHUNK, M, true, true, false, false, true>(P, B, kg, pairs_out, dst, xnew, dkg, mu_all, cov_all,
                                                                  var_all, mux_all, wts, dupv, cov_stride, bpad, b, g,
                                                                  split, smem, kst_slot(dst, P, 2), nullptr, hout);
+  kst_wide_end(dst, P);
 }
 
 template <int M>
@@ -2794,13 +2821,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(env_waves_p
   extern __shared__ __attribute__((aligned(16))) double smem[];
   if (DKG_ABLATIONS && (__builtin_amdgcn_readfirstlane(P->debug_env) & 2)) return;  // ablation: empty envelope stage
   int b, g;
-  if (!xcd_group(blockIdx.x, B, split * ntgt, b, g)) return;
+  if (!xcd_deal(blockIdx.x, B, split * ntgt, b, g)) return;
+  kst_wide_begin(dst, P);
   const int tau = g / split;
   g -= tau * split;
   envelope_body<STREAM_CHUNK, M, true, true, false, true, true>(P, B, kg, pairs_out, dst, xnew, dkg, mu_all, cov_all,
                                                                 var_all, mux_all, wts, dupv, cov_stride, bpad, b, g,
                                                                 split, smem, kst_slot(dst, P, 2), nullptr, hout, tau,
                                                                 ntgt, target_of(tpack, tau));
+  kst_wide_end(dst, P);
 }
 
 // The lines of every (candidate, scalarisation) pair of the plan's last

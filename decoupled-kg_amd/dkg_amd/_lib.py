@@ -206,6 +206,7 @@ SIGNATURES = {
     "dkg_debug_f32_dispatch": (c_int, [c_int] * 6 + [POINTER(c_int)]),
     "dkg_debug_mfma_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "dkg_debug_envelope_lds": (c_int, [c_int] * 9 + [POINTER(c_int)]),
+    "dkg_debug_envelope_deal": (c_int, [c_int] * 3 + [POINTER(c_int)] * 2),
 }
 
 _lib = None

@@ -821,7 +821,10 @@ int dkg_plan_lines(const void* host_plan, const void* dev_plan, const double* xn
 /* Debug: per-workgroup phase stamps of the three forward kernels, written when
  * the env var DKG_DEBUG_STAMPS=1 at plan creation: [3][1024][8] words (slot 0
  * s_memrealtime at start, 1..6 s_memtime at phase boundaries, 7 s_memrealtime
- * at end); n words are copied. */
+ * at end); n words are copied.  DKG_DEBUG_STAMPS=3: the same buffer as [12288][2]
+ * words, written by the envelope launch alone, per workgroup id: s_memrealtime at
+ * start, then s_memrealtime at end in bits 59:0 with the XCD the workgroup ran on
+ * (HW_REG_XCC_ID) in bits 63:60. */
 int dkg_debug_read_kstamps(unsigned long long* host, int n);
 
 /* Debug/self-test of the register-only wave butterflies the kernels use
@@ -900,6 +903,15 @@ int dkg_debug_plan_envelope(const void* host_plan, int out[4]);
 #define DKG_ENV_LDS_REGIONS 20
 int dkg_debug_envelope_lds(int m, int N, int waves, int S, int d, int max_np, int grad, int stream, int grows,
                            int out[DKG_ENV_LDS_REGIONS + 1]);
+
+/* Which (item, member) workgroup id L of an envelope launch over `nitems` items of `groups` workgroups each runs
+ * (csrc/dkg_common.h xcd_deal; the launch has 8 * groups * ceil(nitems / 8) ids, ids L and L + 8 share an XCD):
+ * the members of an item on consecutive ids of one XCD, the items of every aligned eight rotated over the launch
+ * residues so that item b runs on residue (b + b / 8 + b / 64) mod 8.  Returns 1 and sets *item, *member for an id
+ * that runs an item, 0 for a padding id (*item >= nitems then), -2 for a NULL pointer, nitems < 1, groups < 1, a
+ * launch of 2^31 ids or more, or L outside the launch (dkg_last_error).  Host only: the arithmetic the kernels
+ * run. */
+int dkg_debug_envelope_deal(int L, int nitems, int groups, int* item, int* member);
 
 /* ---- Launcher: captured forward graphs of several streams enqueued side by side from host threads.
  * A hipGraphLaunch costs ~1 us of host time per kernel node plus ~9 us; one thread launching every
