@@ -1562,6 +1562,126 @@ __host__ __device__ constexpr int env_waves_per_eu(int maxl, int m, bool grad, b
   return (grad || stream || maxl > 17) ? 2 : (m >= 8 && maxl > 8) ? 3 : DKG_ENV_FWD_WPE;  // m = 8: 3 spill-free
 }
 
+// ---- the pieces the envelope's phases share (each the one statement of its fma chain)
+
+// sum_i c[i] r_i over one line record r (weights c): the outputs in output order (the FMA order of the
+// reference's weighted sums), two per 16-byte read.  PS: doubles between two component pairs (2: a record
+// [cov_rec(M)]; the staged chunks keep each pair in a plane of its own).
+template <int M, int PS = 2>
+__device__ __forceinline__ double rec_dot(const double* r, const double (&c)[M], double acc) {
+  if constexpr (cov_rec(M) == 1) {
+    acc = fma(c[0], r[0], acc);
+  } else {
+#pragma unroll
+    for (int q = 0; 2 * q < M; ++q) {
+      const double2 u = *reinterpret_cast<const double2*>(r + (size_t)q * PS);
+      acc = fma(c[2 * q], u.x, acc);
+      if (2 * q + 1 < M) acc = fma(c[2 * q + 1], u.y, acc);
+    }
+  }
+  return acc;
+}
+
+// Line 0, the candidate itself (discretekg.py:182-183): a = a_off + sum_i wa_i m0_i, b = sum_i wb_i v0_i over
+// its own posterior mean and variance, or over the record it coincides with.
+template <int M>
+__device__ __forceinline__ void line0(const double (&wa)[M], const double (&wb)[M], double a_off,
+                                      const double (&m0)[M], const double (&v0)[M], double& a, double& bb) {
+  a = a_off;
+  bb = 0.0;
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    a = fma(wa[i], m0[i], a);
+    bb = fma(wb[i], v0[i], bb);
+  }
+}
+
+// The target output's slope weight by selects (no dynamic index into the SGPR array).
+template <int M>
+__device__ __forceinline__ double target_weight(const double (&wb)[M], int target) {
+  double wbt = 0.0;
+#pragma unroll
+  for (int i = 0; i < M; ++i) wbt = (i == target) ? wb[i] : wbt;
+  return wbt;
+}
+
+// One staged chunk (SCH lines) of both record arrays into bm = [mu | cov], CBL doubles each, by a transposing
+// DMA: position p of plane q2 holds component pair q2 of record rec_of(p), clamped into 0 .. N-1 (the clamped
+// positions are line 0, built from registers, and padding lines); one instruction = 64 positions of one plane.
+template <int M, int SCH, class RecOf>
+__device__ __forceinline__ void dma_chunk_planes(const double* mu, const double* cv, double* bm, int CBL, int N,
+                                                 int wave, int SW, int lane, RecOf rec_of) {
+  static_assert(stream_staged(M), "the staged-streaming forward only (records of whole component pairs)");
+  constexpr int MP = cov_rec(M), NP2 = MP / 2, GR = SCH / 64, NI = NP2 * GR;
+  for (int ii = wave; ii < 2 * NI; ii += SW) {
+    const int arr = ii / NI, rem = ii % NI, q2 = rem / GR, gi = rem % GR;
+    const double* src = arr ? cv : mu;
+    const int rec = min(max(rec_of(gi * 64 + lane), 0), N - 1);
+    __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(src + (size_t)rec * MP + 2 * q2),
+                                     reinterpret_cast<__attribute__((address_space(3))) void*>(
+                                         reinterpret_cast<uintptr_t>(bm + (size_t)arr * CBL +
+                                                                     ((size_t)q2 * SCH + gi * 64) * 2)),
+                                     16, 0, 0);
+  }
+}
+
+// ---- phase (GRAD): d v_i / dx into sgv [M][16].  GROWS: the rows read where the cross stage left them.
+template <bool GROWS>
+__device__ __forceinline__ void env_dv_setup(const Plan* __restrict__ P, int b, int bpad, int m, int d, int NP, int NPS,
+                                             int SW, int wave, int lane_k, const double* qrow, const double* jrow,
+                                             double* sgv) {
+  // d v_i / dx = -2 J_i^T q_i (model space), one (output, coordinate) per wave
+  for (int pidx = wave; pidx < m * d; pidx += SW) {
+    const int i = pidx / d, dd = pidx % d;
+    double acc = 0.0;
+    if constexpr (GROWS) {
+      // the staged rows' sum over all of NP: columns npi .. NP-1 (the tail the staged body zeroes) enter as 0
+      const int npi = pad16(P->o[i].n);
+      const double* qg = P->qxrm[i] + (size_t)b * npi;
+      const double* jg = P->jq[i] + ((size_t)dd * bpad + b) * npi;
+      for (int c = lane_k; c < NP; c += 64) {
+        const int cc = min(c, npi - 1);
+        const double jv = (c < npi) ? jg[cc] : 0.0, qv = (c < npi) ? qg[cc] : 0.0;
+        acc = fma(jv, qv, acc);
+      }
+    } else {
+      for (int c = lane_k; c < NP; c += 64) acc = fma(jrow[((size_t)i * d + dd) * NPS + c], qrow[(size_t)i * NPS + c], acc);
+    }
+    acc = wave_sum(acc);
+    if (lane_k == 0) sgv[i * DKG_MAX_DIM + dd] = -2.0 * acc;
+  }
+}
+
+// ---- phase (HO, the fused forward): count this envelope workgroup into the launch's done counter.
+__device__ __forceinline__ void fused_counters_rezero(const Plan* __restrict__ P, const Handoff* ho) {
+  // launch done when every envelope workgroup has counted itself: the last re-zeroes the counters
+  // for the next launch on this plan (stream-ordered after this one)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long prev =
+        __hip_atomic_fetch_add(ho->done, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (prev + 1 == ho->quota_done) {
+      for (int i = 0; i < P->m * ho->rt; ++i)
+        __hip_atomic_store(ho->cnt1 + (size_t)i * HANDOFF_STRIDE, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      for (int i = 0; i < ho->nrb; ++i)
+        __hip_atomic_store(ho->cnt2 + (size_t)i * HANDOFF_STRIDE, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(ho->done, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+// The kernel arguments of the envelope kernels, in the order the tools and the launch helper know (the line data,
+// the candidate posteriors and the weights beside the plan pointer, so the body's first DMA issues after this one
+// kernel-argument load), and the same names handed on to the body.
+#define DKG_ENV_PARAMS                                                                                            \
+  const Plan* __restrict__ P, int B, double* __restrict__ kg, double* __restrict__ pairs_out, int dst,            \
+      const double* __restrict__ xnew, double* __restrict__ dkg, const double* __restrict__ mu_all,               \
+      const double* __restrict__ cov_all, const double* __restrict__ var_all, const double* __restrict__ mux_all, \
+      const double* __restrict__ wts, const int* __restrict__ dupv, long long cov_stride, int bpad,               \
+      double* __restrict__ hout, int split
+#define DKG_ENV_ARGS \
+  P, B, kg, pairs_out, dst, xnew, dkg, mu_all, cov_all, var_all, mux_all, wts, dupv, cov_stride, bpad, hout, split
 
 // GRAD: also dKG/dx_b (envelope theorem; include/dkg.h dkg_plan_forward_grad),
 // accumulated into dkg[b x d]; the extra LDS follows the survivor lists.
@@ -1580,16 +1700,8 @@ __host__ __device__ constexpr int env_waves_per_eu(int maxl, int m, bool grad, b
 // in the same column order into the same fma chains: the staged-rows streaming GRAD kernel's bits, for models
 // whose rows do not fit in LDS.
 template <int MAXL, int M, bool GRAD, bool STREAM, bool HO = false, bool MT = false, bool GROWS = false>
-__device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B, double* __restrict__ kg,
-                                              double* __restrict__ pairs_out, int dst,
-                                              const double* __restrict__ xnew, double* __restrict__ dkg,
-                                              const double* __restrict__ mu_all, const double* __restrict__ cov_all,
-                                              const double* __restrict__ var_all,
-                                              const double* __restrict__ mux_all, const double* __restrict__ wts,
-                                              const int* __restrict__ dupv, long long cov_stride, int bpad, int b,
-                                              int g, int G, double* smem, unsigned long long* st,
-                                              const Handoff* ho = nullptr, double* __restrict__ hout = nullptr,
-                                              int tau = 0, int ntgt = 1, int target_mt = -1) {
+__device__ __forceinline__ void envelope_body(DKG_ENV_PARAMS, int b, int g, int tau, int ntgt, int target_mt,
+                                              double* smem, unsigned long long* st, const Handoff* ho = nullptr) {
   static_assert(!HO || (!GRAD && !STREAM), "the fused forward stages its lines (no gradient, no streaming)");
   static_assert(!GROWS || (GRAD && STREAM), "global rows: the streaming gradient envelope only");
   // per output i: y_std, y_mean, noise, outputscale, noiseless variance at x_b, mean at x_b (model space),
@@ -1625,6 +1737,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
     cv_src[i] = cov_all + (size_t)b * cov_stride;  // records of candidate b
   }
 
+  // ==== phase 1 (all modes): region pointers
   // the dynamic LDS regions (EnvLds)
   constexpr int MP = cov_rec(M);  // doubles per line record
   const int d = P->d;
@@ -1665,6 +1778,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
     shk = reinterpret_cast<int*>(region(L.shk));
   }
 
+  // ==== phase 2 (all modes): staging prologue
   // ---- one round of memory traffic: DMA the line data, plain loads for the rest
   // per-output scalars and the candidate's own posterior (variance from the
   // covariance stage, mean from the cross stage): lane i of wave 0 loads output i
@@ -1827,12 +1941,8 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
       double w[M], wa[M], wb[M];
       double a_off, den;
       pair_coefs<M>(c_w, m, full, target, c_ysd, c_ymu, c_nz, c_sv, w, wa, wb, a_off, den);
-      double a0 = a_off, b0 = 0.0;  // line 0 from the candidate's own posterior (no coincidence)
-#pragma unroll
-      for (int i = 0; i < M; ++i) {
-        a0 = fma(wa[i], c_mx[i], a0);
-        b0 = fma(wb[i], c_sv[i], b0);
-      }
+      double a0, b0;  // line 0 from the candidate's own posterior (no coincidence)
+      line0<M>(wa, wb, a_off, c_mx, c_sv, a0, b0);
       if (lane_k < j1 - j0) {
         double* row = sbuf + (size_t)lane_k * 2 * LC;
 #pragma unroll
@@ -1895,6 +2005,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
   }
   if (!GRAD) KST(st, 3);
 
+  // (all modes) this wave's part of the per-wave regions
   double* sb = sbuf + (size_t)wave * 2 * LC;
   double* sa = sb + LC;
   // staged streaming forward: the chunk buffers and the refinement's vertex arrays share cbuf (the refinement
@@ -1906,33 +2017,16 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
   int* sif = reinterpret_cast<int*>(smem + L.sif) + (size_t)wave * LC;  // forward (GRAD: sidx)
   int* si = nullptr;
   double* gw = nullptr;
+  // ==== phase 3 (GRAD): d v_i / dx (env_dv_setup)
   if constexpr (GRAD) {
     si = sidx + (size_t)wave * ENV_CAP;
     gw = sgw + wave * 64;
-    // d v_i / dx = -2 J_i^T q_i (model space), one (output, coordinate) per wave
-    for (int pidx = wave; pidx < m * d; pidx += SW) {
-      const int i = pidx / d, dd = pidx % d;
-      double acc = 0.0;
-      if constexpr (GROWS) {
-        // the staged rows' sum over all of NP: columns npi .. NP-1 (the tail the staged body zeroes) enter as 0
-        const int npi = pad16(P->o[i].n);
-        const double* qg = P->qxrm[i] + (size_t)b * npi;
-        const double* jg = P->jq[i] + ((size_t)dd * bpad + b) * npi;
-        for (int c = lane_k; c < NP; c += 64) {
-          const int cc = min(c, npi - 1);
-          const double jv = (c < npi) ? jg[cc] : 0.0, qv = (c < npi) ? qg[cc] : 0.0;
-          acc = fma(jv, qv, acc);
-        }
-      } else {
-        for (int c = lane_k; c < NP; c += 64) acc = fma(jrow[((size_t)i * d + dd) * NPS + c], qrow[(size_t)i * NPS + c], acc);
-      }
-      acc = wave_sum(acc);
-      if (lane_k == 0) sgv[i * DKG_MAX_DIM + dd] = -2.0 * acc;
-    }
+    env_dv_setup<GROWS>(P, b, bpad, m, d, NP, NPS, SW, wave, lane_k, qrow, jrow, sgv);
     gw[lane_k] = 0.0;
     __syncthreads();
     KST(st, 2);
   }
+  // ==== phase 4 (all modes): per-output constants into SGPR arrays
   // One pair per wave, written as a one-shot block: nothing pair-invariant (psi's coefficients, lane
   // addresses) is hoisted out of a loop and kept live in registers.
   // sv / mx0: the candidate's noiseless variance and mean (the slopes' normaliser, the gradient);
@@ -1961,6 +2055,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
     l0v[i] = sgpr_f64(live ? s_pp[i * NPP + 7] : 0.0);
   }
 
+  // ==== phase 5 (STG: the streaming forward of M = 2 .. 4): staged-streaming passes
   // ---- staged streaming forward: the extremes pass and the filter pass of every pair of the workgroup
   // over LDS-staged chunks of the line records (chunk q: lines q*SCH .. q*SCH + SCH - 1, records k - 1),
   // the next chunk's DMA in flight while the current one is read; the survivor lists then go to the
@@ -1981,31 +2076,15 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
       wb[i] = sgpr_f64(wb[i]);
     }
     a_off = sgpr_f64(a_off);
-    double bb0 = 0.0, a0 = a_off, wbt = 0.0;
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-      bb0 = fma(wb[i], l0v[i], bb0);
-      a0 = fma(wa[i], l0m[i], a0);
-      wbt = (i == target) ? wb[i] : wbt;
-    }
+    double bb0, a0;
+    line0<M>(wa, wb, a_off, l0m, l0v, a0, bb0);
+    const double wbt = target_weight<M>(wb, target);
     const int nq = (NL + SCH - 1) / SCH;
     const double* cvb = cov_all + (size_t)b * cov_stride;
-    // chunk q's records into buffer q & 1 by a transposing DMA: position p of plane q2 holds component
-    // pair q2 of record q*SCH - 1 + p (line q*SCH + p; clamped into 0 .. N-1, the clamped positions are
-    // line 0, built from registers, and padding lines); one instruction = 64 positions of one plane
+    // chunk q's records (position p: record q*SCH - 1 + p, line q*SCH + p) into buffer q & 1
     auto stage = [&](int q) {
-      constexpr int NP2 = MP / 2, GR = SCH / 64, NI = NP2 * GR;
-      double* bm = cbuf + (size_t)(q & 1) * 2 * CBL;
-      for (int ii = wave; ii < 2 * NI; ii += SW) {
-        const int arr = ii / NI, rem = ii % NI, q2 = rem / GR, gi = rem % GR;
-        const double* src = arr ? cvb : mu_all;
-        const int rec = min(max(q * SCH - 1 + gi * 64 + lane_k, 0), N - 1);
-        __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(src + (size_t)rec * MP + 2 * q2),
-                                         reinterpret_cast<__attribute__((address_space(3))) void*>(
-                                             reinterpret_cast<uintptr_t>(bm + (size_t)arr * CBL +
-                                                                         ((size_t)q2 * SCH + gi * 64) * 2)),
-                                         16, 0, 0);
-      }
+      dma_chunk_planes<M, SCH>(mu_all, cvb, cbuf + (size_t)(q & 1) * 2 * CBL, CBL, N, wave, SW, lane_k,
+                               [&](int p) { return q * SCH - 1 + p; });
     };
     // build_chunk's lines (same arithmetic, same order) from the staged records of chunk q
     auto build_staged = [&](int q, double (&la)[CS], double (&lb)[CS]) {
@@ -2016,27 +2095,18 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
       // 16-byte reads, consecutive across the wave; components i >= m carry zero weights over zero
       // padding, so the sums are build_chunk's.  The full / target choice outside the slot loop: one LDS
       // read stream, no wait per slot.
-      auto adot = [&](const double* r, const double (&c)[M], double acc) __attribute__((always_inline)) {
-#pragma unroll
-        for (int q2 = 0; 2 * q2 < M; ++q2) {
-          const double2 u = *reinterpret_cast<const double2*>(r + (size_t)q2 * SCH * 2);
-          acc = fma(c[2 * q2], u.x, acc);
-          if (2 * q2 + 1 < M) acc = fma(c[2 * q2 + 1], u.y, acc);
-        }
-        return acc;
-      };
       const int tg = full ? 0 : target;
       const double* cvt = cvr + (size_t)(tg >> 1) * SCH * 2 + (tg & 1);  // target path
       if (full) {
 #pragma unroll
         for (int t = 0; t < CS; ++t) {
-          la[t] = adot(mur + 128 * t, wa, a_off);
-          lb[t] = adot(cvr + 128 * t, wb, 0.0);
+          la[t] = rec_dot<M, 2 * SCH>(mur + 128 * t, wa, a_off);
+          lb[t] = rec_dot<M, 2 * SCH>(cvr + 128 * t, wb, 0.0);
         }
       } else {
 #pragma unroll
         for (int t = 0; t < CS; ++t) {
-          la[t] = adot(mur + 128 * t, wa, a_off);
+          la[t] = rec_dot<M, 2 * SCH>(mur + 128 * t, wa, a_off);
           lb[t] = fma(wbt, cvt[128 * t], 0.0);
         }
       }
@@ -2057,19 +2127,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
     // out as chunk 0) staged in buffer 0 by one strided DMA, then per wave the sample's extremes and
     // SH_ROUNDS quickhull rounds in registers; the vertex chain (lines of the set) goes to buffer 1.
     const int stride = (NL + SCH - 1) / SCH;
-    {
-      constexpr int NP2 = MP / 2, GR = SCH / 64, NI = NP2 * GR;
-      for (int ii = wave; ii < 2 * NI; ii += SW) {
-        const int arr = ii / NI, rem = ii % NI, q2 = rem / GR, gi = rem % GR;
-        const double* src = arr ? cvb : mu_all;
-        const int rec = min(max((gi * 64 + lane_k) * stride - 1, 0), N - 1);
-        __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(src + (size_t)rec * MP + 2 * q2),
-                                         reinterpret_cast<__attribute__((address_space(3))) void*>(
-                                             reinterpret_cast<uintptr_t>(cbuf + (size_t)arr * CBL +
-                                                                         ((size_t)q2 * SCH + gi * 64) * 2)),
-                                         16, 0, 0);
-      }
-    }
+    dma_chunk_planes<M, SCH>(mu_all, cvb, cbuf, CBL, N, wave, SW, lane_k, [&](int p) { return p * stride - 1; });
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     ChainChords<SH_NC> cc;
@@ -2138,6 +2196,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
 
   if (const int j = j0 + wave; j < j1) {
     const int lane = lane_k;
+    // ==== phase 6 (per pair, all modes): pair coefficients and the line builders
     // ---- line coefficients (wave uniform; shared with lines_export_kernel)
     double w[M], wa[M], wb[M];
     double a_off, den;
@@ -2166,17 +2225,11 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
     a_off = sgpr_f64(a_off);
     den = sgpr_f64(den);
     // line 0: the candidate itself (discretekg.py:182-183), or the record it coincides with
-    auto line0 = [&](double& a, double& bb) __attribute__((always_inline)) {
-      a = a_off;
-      bb = 0.0;
-#pragma unroll
-      for (int i = 0; i < M; ++i) {
-        a = fma(wa[i], l0m[i], a);
-        bb = fma(wb[i], l0v[i], bb);
-      }
+    auto line0w = [&](double& a, double& bb) __attribute__((always_inline)) {
+      line0<M>(wa, wb, a_off, l0m, l0v, a, bb);
     };
     if constexpr (COEF1) {
-      if (dupk != DUP_NONE) line0(a0l, b0l);  // (uniform) the same chains over the record's components
+      if (dupk != DUP_NONE) line0w(a0l, b0l);  // (uniform) the same chains over the record's components
       a0l = sgpr_f64(a0l);
       b0l = sgpr_f64(b0l);
     }
@@ -2214,9 +2267,8 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
         }
       }
       if (c == 0) {
-        double a = a_off;  // line 0: the candidate itself (discretekg.py:182-183)
-#pragma unroll
-        for (int i = 0; i < M; ++i) a = fma(wa[i], l0m[i], a);
+        double a, bb;  // line 0's intercept alone is used: bb is discarded (its slope is bb0, above)
+        line0w(a, bb);
         la[0] = (lane == 0) ? a : la[0];
         lb[0] = (lane == 0) ? bb0 : lb[0];
       }
@@ -2227,40 +2279,24 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
       // reference's weighted sums), two per 16-byte read; components >= m are zero with zero weight
       const double* mur = lmu + (lane - 1) * MP;
       const double* cvr = lcv + (lane - 1) * MP;
-      // sum_i c[i] r_i over record r (weights c)
-      auto rec_dot = [&](const double* r, const double (&c)[M], double acc) __attribute__((always_inline)) {
-        if constexpr (MP == 1) {
-          acc = fma(c[0], r[0], acc);
-        } else {
-#pragma unroll
-          for (int q = 0; 2 * q < M; ++q) {
-            const double2 u = *reinterpret_cast<const double2*>(r + 2 * q);
-            acc = fma(c[2 * q], u.x, acc);
-            if (2 * q + 1 < M) acc = fma(c[2 * q + 1], u.y, acc);
-          }
-        }
-        return acc;
-      };
       if (full) {
 #pragma unroll
         for (int t = 0; t < MAXL; ++t) {
-          la[t] = rec_dot(mur + 64 * MP * t, wa, a_off);
-          lb[t] = rec_dot(cvr + 64 * MP * t, wb, 0.0);
+          la[t] = rec_dot<M>(mur + 64 * MP * t, wa, a_off);
+          lb[t] = rec_dot<M>(cvr + 64 * MP * t, wb, 0.0);
         }
       } else {
         const double* cvt = cvr + target;
-        double wbt = 0.0;
-#pragma unroll
-        for (int i = 0; i < M; ++i) wbt = (i == target) ? wb[i] : wbt;
+        const double wbt = target_weight<M>(wb, target);
 #pragma unroll
         for (int t = 0; t < MAXL; ++t) {
-          la[t] = rec_dot(mur + 64 * MP * t, wa, a_off);
+          la[t] = rec_dot<M>(mur + 64 * MP * t, wa, a_off);
           lb[t] = wbt * cvt[64 * MP * t];
         }
       }
       {
         double a = a0l, bb = b0l;
-        if constexpr (!COEF1) line0(a, bb);
+        if constexpr (!COEF1) line0w(a, bb);
         la[0] = (lane == 0) ? a : la[0];
         lb[0] = (lane == 0) ? bb : lb[0];
       }
@@ -2269,6 +2305,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
 
     double kgj;
     int hn = 1;  // upper-envelope lines of this pair (recorded with kg_pairs)
+    // ==== phase 7 (GRAD): gradient pair; phase 8 (forward): the STG tail, the STREAM variant, the staged variant
     if constexpr (GRAD) {
       EnvFilter f;
       if constexpr (STREAM) {
@@ -2512,7 +2549,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
           sumDb = hg.sumDb;
           nh = hg.nq;
           f.cntT = hg.cntT;
-          if (lane == 0) {  // line 0 (the candidate): d b_0 and d a_0 terms
+          if (lane == 0) {
             for (int dd = 0; dd < d; ++dd) {
               double gvs = 0.0;
 #pragma unroll
@@ -2533,9 +2570,8 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
         if (nh > 0) flush();
         if (j == j0 + wave) KST(st, 5);
         // - sum_e Dw_e b_e * dV/(2V), - [line 0 attains max a] da_0/dx
-        double a0 = a_off;
-#pragma unroll
-        for (int i = 0; i < M; ++i) a0 = fma(wa[i], l0m[i], a0);
+        double a0, b0;  // line 0's intercept alone is used: b0 is discarded
+        line0w(a0, b0);
         const double tfac = (a0 == f.aT) ? 1.0 / (double)f.cntT : 0.0;
         if (lane == 0)
           for (int dd = 0; dd < d; ++dd) gw[48 + dd] += gw[dd] - sumDb * gw[32 + dd] - tfac * gw[16 + dd];
@@ -2570,7 +2606,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
       TopHint hint{false, 0.0, 0.0};
       if (HINT && flat_ok && P->itop != nullptr) {
         double a0 = a0l, b0 = b0l;
-        if constexpr (!COEF1) line0(a0, b0);
+        if constexpr (!COEF1) line0w(a0, b0);
         const double A1 = hA1;
         const int k1 = hk1, c1 = hc1;
         if (a0 > A1) {
@@ -2578,24 +2614,11 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
         } else if (a0 < A1 && c1 == 1) {
           // line k1's slope, as the build computes it (record k1 - 1)
           const double* r = lcv + (size_t)(k1 - 1) * MP;
-          double bk = 0.0;
-          if (full) {
-            if constexpr (MP == 1) {
-              bk = fma(wb[0], r[0], bk);
-            } else {
-#pragma unroll
-              for (int q = 0; 2 * q < M; ++q) {
-                const double2 u = *reinterpret_cast<const double2*>(r + 2 * q);
-                bk = fma(wb[2 * q], u.x, bk);
-                if (2 * q + 1 < M) bk = fma(wb[2 * q + 1], u.y, bk);
-              }
-            }
-          } else {
-            double wbt = 0.0;
-#pragma unroll
-            for (int i = 0; i < M; ++i) wbt = (i == target) ? wb[i] : wbt;
-            bk = wbt * r[target];
-          }
+          double bk;
+          if (full)
+            bk = rec_dot<M>(r, wb, 0.0);
+          else
+            bk = target_weight<M>(wb, target) * r[target];
           hint = TopHint{true, A1, bk};
         }
       }
@@ -2615,6 +2638,7 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
     if (lane == 0) skg[j - j0] = kgj;
   }
 
+  // ==== phase 9 (all modes): combine over S
   // ---- mean over S: per-wave sums -> per-WG sum (fixed order) -> across WGs
 #ifndef DKG_STG_STAMPS
   if (!GRAD) KST(st, 4);
@@ -2708,129 +2732,81 @@ __device__ __forceinline__ void envelope_body(const Plan* __restrict__ P, int B,
       }
     }
   }
-  if constexpr (HO) {
-    // launch done when every envelope workgroup has counted itself: the last re-zeroes the counters
-    // for the next launch on this plan (stream-ordered after this one)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const unsigned long long prev =
-          __hip_atomic_fetch_add(ho->done, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (prev + 1 == ho->quota_done) {
-        for (int i = 0; i < P->m * ho->rt; ++i)
-          __hip_atomic_store(ho->cnt1 + (size_t)i * HANDOFF_STRIDE, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (int i = 0; i < ho->nrb; ++i)
-          __hip_atomic_store(ho->cnt2 + (size_t)i * HANDOFF_STRIDE, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(ho->done, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-    }
-  }
+  // ==== phase 10 (HO): the fused launch's counters
+  if constexpr (HO) fused_counters_rezero(P, ho);
   if (st) __syncthreads();  // workgroup-uniform: the end stamp covers every wave
   KST_END(st);
 }
 
-template <int MAXL, int M, bool GRAD, bool STREAM>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(env_waves_per_eu(MAXL, M, GRAD, STREAM)))) void envelope_kernel(const Plan* __restrict__ P, int B, double* __restrict__ kg,
-                                                       double* __restrict__ pairs_out, int dst,
-                                                       const double* __restrict__ xnew, double* __restrict__ dkg,
-                                                       const double* __restrict__ mu_all,
-                                                       const double* __restrict__ cov_all,
-                                                       const double* __restrict__ var_all,
-                                                       const double* __restrict__ mux_all,
-                                                       const double* __restrict__ wts,
-                                                       const int* __restrict__ dupv, long long cov_stride,
-                                                       int bpad, double* __restrict__ hout, int split) {
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  if (DKG_ABLATIONS && (__builtin_amdgcn_readfirstlane(P->debug_env) & 2)) return;  // ablation: empty envelope stage
-  // 1-D grid: the `split` workgroups of one candidate side by side on one XCD, so its line
-  // records come from HBM once and from that XCD's L2 for the others; the candidates dealt over the XCDs by
-  // xcd_deal, not xcd_group: the stage's work depends on the data
-  int b, g;
-  if (!xcd_deal(blockIdx.x, B, split, b, g)) return;
+#define DKG_ENV_KERNEL(MAXL, M, GRAD, STREAM) \
+  __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(env_waves_per_eu(MAXL, M, GRAD, STREAM)))) void
+
+// What every entry kernel does before the body: its item.  1-D grid: the `split` workgroups of one candidate side
+// by side on one XCD, so its line records come from HBM once and from that XCD's L2 for the others; the candidates
+// dealt over the XCDs by xcd_deal, not xcd_group: the stage's work depends on the data.  MT (a plan of ntgt > 1
+// targets): ntgt * split workgroups per candidate side by side (member = tau * split + g), so the candidate's
+// records come from HBM once for all of its items.  False: the workgroup has nothing to do.
+// (The kernels call the body themselves: through a shared entry function that also made the call, the M = 1
+// gradient kernels came out 1.0 to 1.5 % longer.)
+template <bool MT>
+__device__ __forceinline__ bool envelope_item(const Plan* __restrict__ P, int B, int dst, int split, int ntgt, int& b,
+                                              int& g, int& tau) {
+  if (DKG_ABLATIONS && (__builtin_amdgcn_readfirstlane(P->debug_env) & 2)) return false;  // ablation: empty envelope stage
+  if (!xcd_deal(blockIdx.x, B, MT ? split * ntgt : split, b, g)) return false;
   kst_wide_begin(dst, P);
-  envelope_body<MAXL, M, GRAD, STREAM>(P, B, kg, pairs_out, dst, xnew, dkg, mu_all, cov_all, var_all, mux_all, wts,
-                                       dupv, cov_stride, bpad, b, g, split, smem, kst_slot(dst, P, 2), nullptr, hout);
+  tau = 0;
+  if constexpr (MT) {
+    tau = g / split;
+    g -= tau * split;
+  }
+  return true;
+}
+
+template <int MAXL, int M, bool GRAD, bool STREAM>
+DKG_ENV_KERNEL(MAXL, M, GRAD, STREAM) envelope_kernel(DKG_ENV_PARAMS) {
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  int b, g, tau;
+  if (!envelope_item<false>(P, B, dst, split, 1, b, g, tau)) return;
+  envelope_body<MAXL, M, GRAD, STREAM>(DKG_ENV_ARGS, b, g, tau, 1, -1, smem, kst_slot(dst, P, 2));
   kst_wide_end(dst, P);
 }
 
-// The envelope stage of a plan of ntgt > 1 targets: ntgt * split workgroups per candidate, side by side on one
-// XCD (member = tau * split + g), so the candidate's records come from HBM once for all of its items.  The same
-// body, so an item's bits are the single-target kernel's.
+// The envelope stage of a plan of ntgt > 1 targets: the same body, so an item's bits are the single-target kernel's.
 template <int MAXL, int M, bool GRAD, bool STREAM>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(env_waves_per_eu(MAXL, M, GRAD, STREAM)))) void envelope_targets_kernel(const Plan* __restrict__ P, int B, double* __restrict__ kg,
-                                                       double* __restrict__ pairs_out, int dst,
-                                                       const double* __restrict__ xnew, double* __restrict__ dkg,
-                                                       const double* __restrict__ mu_all,
-                                                       const double* __restrict__ cov_all,
-                                                       const double* __restrict__ var_all,
-                                                       const double* __restrict__ mux_all,
-                                                       const double* __restrict__ wts,
-                                                       const int* __restrict__ dupv, long long cov_stride,
-                                                       int bpad, double* __restrict__ hout, int split,
-                                                       int ntgt, unsigned long long tpack) {
+DKG_ENV_KERNEL(MAXL, M, GRAD, STREAM) envelope_targets_kernel(DKG_ENV_PARAMS, int ntgt, unsigned long long tpack) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  if (DKG_ABLATIONS && (__builtin_amdgcn_readfirstlane(P->debug_env) & 2)) return;  // ablation: empty envelope stage
-  int b, g;
-  if (!xcd_deal(blockIdx.x, B, split * ntgt, b, g)) return;
-  kst_wide_begin(dst, P);
-  const int tau = g / split;
-  g -= tau * split;
-  envelope_body<MAXL, M, GRAD, STREAM, false, true>(P, B, kg, pairs_out, dst, xnew, dkg, mu_all, cov_all, var_all,
-                                                    mux_all, wts, dupv, cov_stride, bpad, b, g, split, smem,
-                                                    kst_slot(dst, P, 2), nullptr, hout, tau, ntgt,
-                                                    target_of(tpack, tau));
+  int b, g, tau;
+  if (!envelope_item<true>(P, B, dst, split, ntgt, b, g, tau)) return;
+  envelope_body<MAXL, M, GRAD, STREAM, false, true>(DKG_ENV_ARGS, b, g, tau, ntgt, target_of(tpack, tau), smem,
+                                                    kst_slot(dst, P, 2));
   kst_wide_end(dst, P);
 }
 
 // The streaming value+gradient envelope with global rows (envelope_body GROWS; DKG_PLAN_GRAD_GLOBAL_ROWS): kernels of
 // their own, so every other instantiation keeps its name and its code.  One target, and items (tau, b).
 template <int M>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(env_waves_per_eu(STREAM_CHUNK, M, true, true)))) void envelope_rows_kernel(const Plan* __restrict__ P, int B, double* __restrict__ kg,
-                                                       double* __restrict__ pairs_out, int dst,
-                                                       const double* __restrict__ xnew, double* __restrict__ dkg,
-                                                       const double* __restrict__ mu_all,
-                                                       const double* __restrict__ cov_all,
-                                                       const double* __restrict__ var_all,
-                                                       const double* __restrict__ mux_all,
-                                                       const double* __restrict__ wts,
-                                                       const int* __restrict__ dupv, long long cov_stride,
-                                                       int bpad, double* __restrict__ hout, int split) {
+DKG_ENV_KERNEL(STREAM_CHUNK, M, true, true) envelope_rows_kernel(DKG_ENV_PARAMS) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  if (DKG_ABLATIONS && (__builtin_amdgcn_readfirstlane(P->debug_env) & 2)) return;  // ablation: empty envelope stage
-  int b, g;
-  if (!xcd_deal(blockIdx.x, B, split, b, g)) return;
-  kst_wide_begin(dst, P);
-  envelope_body<STREAM_CHUNK, M, true, true, false, false, true>(P, B, kg, pairs_out, dst, xnew, dkg, mu_all, cov_all,
-                                                                 var_all, mux_all, wts, dupv, cov_stride, bpad, b, g,
-                                                                 split, smem, kst_slot(dst, P, 2), nullptr, hout);
+  int b, g, tau;
+  if (!envelope_item<false>(P, B, dst, split, 1, b, g, tau)) return;
+  envelope_body<STREAM_CHUNK, M, true, true, false, false, true>(DKG_ENV_ARGS, b, g, tau, 1, -1, smem,
+                                                                 kst_slot(dst, P, 2));
   kst_wide_end(dst, P);
 }
 
 template <int M>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(env_waves_per_eu(STREAM_CHUNK, M, true, true)))) void envelope_rows_targets_kernel(const Plan* __restrict__ P, int B, double* __restrict__ kg,
-                                                       double* __restrict__ pairs_out, int dst,
-                                                       const double* __restrict__ xnew, double* __restrict__ dkg,
-                                                       const double* __restrict__ mu_all,
-                                                       const double* __restrict__ cov_all,
-                                                       const double* __restrict__ var_all,
-                                                       const double* __restrict__ mux_all,
-                                                       const double* __restrict__ wts,
-                                                       const int* __restrict__ dupv, long long cov_stride,
-                                                       int bpad, double* __restrict__ hout, int split,
-                                                       int ntgt, unsigned long long tpack) {
+DKG_ENV_KERNEL(STREAM_CHUNK, M, true, true) envelope_rows_targets_kernel(DKG_ENV_PARAMS, int ntgt,
+                                                                          unsigned long long tpack) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  if (DKG_ABLATIONS && (__builtin_amdgcn_readfirstlane(P->debug_env) & 2)) return;  // ablation: empty envelope stage
-  int b, g;
-  if (!xcd_deal(blockIdx.x, B, split * ntgt, b, g)) return;
-  kst_wide_begin(dst, P);
-  const int tau = g / split;
-  g -= tau * split;
-  envelope_body<STREAM_CHUNK, M, true, true, false, true, true>(P, B, kg, pairs_out, dst, xnew, dkg, mu_all, cov_all,
-                                                                var_all, mux_all, wts, dupv, cov_stride, bpad, b, g,
-                                                                split, smem, kst_slot(dst, P, 2), nullptr, hout, tau,
-                                                                ntgt, target_of(tpack, tau));
+  int b, g, tau;
+  if (!envelope_item<true>(P, B, dst, split, ntgt, b, g, tau)) return;
+  envelope_body<STREAM_CHUNK, M, true, true, false, true, true>(DKG_ENV_ARGS, b, g, tau, ntgt, target_of(tpack, tau),
+                                                                smem, kst_slot(dst, P, 2));
   kst_wide_end(dst, P);
 }
+#undef DKG_ENV_KERNEL
+#undef DKG_ENV_ARGS
+#undef DKG_ENV_PARAMS
 
 // The lines of every (candidate, scalarisation) pair of the plan's last
 // cross / covariance stages, as the envelope builds them (dkg_plan_lines):
@@ -2902,39 +2878,29 @@ struct EnvLaunch {
   double* hout;        // GRAD: pinned host [kg | dkg] (dkg_plan_forward_grad_hostx), nullable
 };
 
+// One envelope launch: `single` the kernel of a plan of one target, `targets` its several-target twin.
+template <class KS, class KT>
+hipError_t launch_env_kernels(KS single, KT targets, const EnvLaunch& a) {
+  const Plan& h = *a.host;
+  auto go = [&](auto kern, auto... tail) {
+    raise_lds_limit((const void*)kern, a.lds);
+    hipLaunchKernelGGL(kern, a.grid, a.block, a.lds, a.s, a.dev, a.B, a.kg, a.pairs, a.dst, a.xnew, a.dkg, h.mu_all,
+                       h.cov_all, h.var_all, h.mux_all, h.weights, h.dup, (long long)h.cov_stride, h.bpad, a.hout,
+                       h.split, tail...);
+    return hipGetLastError();
+  };
+  return h.ntgt > 1 ? go(targets, h.ntgt, h.tpack) : go(single);
+}
+
 template <int MAXL, int M, bool GRAD, bool STREAM>
 hipError_t launch_env_t(const EnvLaunch& a) {
-  const Plan& h = *a.host;
-  if (h.ntgt > 1) {
-    raise_lds_limit((const void*)envelope_targets_kernel<MAXL, M, GRAD, STREAM>, a.lds);
-    hipLaunchKernelGGL((envelope_targets_kernel<MAXL, M, GRAD, STREAM>), a.grid, a.block, a.lds, a.s, a.dev, a.B, a.kg,
-                       a.pairs, a.dst, a.xnew, a.dkg, h.mu_all, h.cov_all, h.var_all, h.mux_all, h.weights, h.dup,
-                       (long long)h.cov_stride, h.bpad, a.hout, h.split, h.ntgt, h.tpack);
-    return hipGetLastError();
-  }
-  raise_lds_limit((const void*)envelope_kernel<MAXL, M, GRAD, STREAM>, a.lds);
-  hipLaunchKernelGGL((envelope_kernel<MAXL, M, GRAD, STREAM>), a.grid, a.block, a.lds, a.s, a.dev, a.B, a.kg, a.pairs,
-                     a.dst, a.xnew, a.dkg, h.mu_all, h.cov_all, h.var_all, h.mux_all, h.weights, h.dup,
-                     (long long)h.cov_stride, h.bpad, a.hout, h.split);
-  return hipGetLastError();
+  return launch_env_kernels(envelope_kernel<MAXL, M, GRAD, STREAM>, envelope_targets_kernel<MAXL, M, GRAD, STREAM>, a);
 }
 
 // The global-rows streaming value+gradient envelope of bucket M (Plan::grad_rows).
 template <int M>
 hipError_t launch_env_rows_t(const EnvLaunch& a) {
-  const Plan& h = *a.host;
-  if (h.ntgt > 1) {
-    raise_lds_limit((const void*)envelope_rows_targets_kernel<M>, a.lds);
-    hipLaunchKernelGGL((envelope_rows_targets_kernel<M>), a.grid, a.block, a.lds, a.s, a.dev, a.B, a.kg, a.pairs,
-                       a.dst, a.xnew, a.dkg, h.mu_all, h.cov_all, h.var_all, h.mux_all, h.weights, h.dup,
-                       (long long)h.cov_stride, h.bpad, a.hout, h.split, h.ntgt, h.tpack);
-    return hipGetLastError();
-  }
-  raise_lds_limit((const void*)envelope_rows_kernel<M>, a.lds);
-  hipLaunchKernelGGL((envelope_rows_kernel<M>), a.grid, a.block, a.lds, a.s, a.dev, a.B, a.kg, a.pairs, a.dst, a.xnew,
-                     a.dkg, h.mu_all, h.cov_all, h.var_all, h.mux_all, h.weights, h.dup, (long long)h.cov_stride,
-                     h.bpad, a.hout, h.split);
-  return hipGetLastError();
+  return launch_env_kernels(envelope_rows_kernel<M>, envelope_rows_targets_kernel<M>, a);
 }
 
 // One output bucket M: picks the line-slot instantiation (MAXL) or the

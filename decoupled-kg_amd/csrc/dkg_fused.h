@@ -97,8 +97,9 @@ forward_fused_kernel(FusedArgs a) {
   }
   const int e = id - a.nC - a.nV;
   envelope_body<MAXL, M, false, false, true>(P, a.B, a.kg, nullptr, a.dst, nullptr, nullptr, a.mu_all, a.cov_all,
-                                             a.var_all, a.mux_all, a.wts, a.dup, a.cov_stride, a.bpad, e / a.split,
-                                             e % a.split, a.split, smem, kst_slot_wg(a.dst, P, 2, e), &a.ho);
+                                             a.var_all, a.mux_all, a.wts, a.dup, a.cov_stride, a.bpad, nullptr, a.split,
+                                             e / a.split, e % a.split, 0, 1, -1, smem, kst_slot_wg(a.dst, P, 2, e),
+                                             &a.ho);
 }
 
 // Dynamic LDS of the fused launch: the largest of its roles'.

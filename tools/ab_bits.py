@@ -1,8 +1,8 @@
 """Bit-identity of two builds of libdkg.so (DKG_LIB A/B): forward KG, KG per pair and the value+gradient
 path on several workloads, then the acquisition layer (posterior mean, sample paths, NSGA-II, ranks, JES, HVKG,
 boxes) at small ragged shapes in every dimension bucket and covariance family, then the core entries' host side
-(state preparation with a jitter retry inside the batch, the MLL, an append, and plans that take every section of
-the plan workspace).
+(state preparation with a jitter retry inside the batch, the MLL, an append, plans that take every section of
+the plan workspace, and under envelope/ the envelope kernels' modes at tiny shapes).
 
 Run on the GPU box from the repo root:
     python tools/ab_bits.py <libA.so> <libB.so> [--acq-only|--core-only] [--json OUT]
@@ -153,6 +153,64 @@ def dump_core(out):
     Xb, kg = rnd(512, d).to(dev), torch.empty(512, dtype=torch.double, device=dev)
     DeviceGPState(ModelListGPState(*plain), rnd(20, d), dev).plan(W(3), None, 512).forward_batches_into(Xb, kg, 16)
     out["core/batches/kg"] = kg.cpu()
+    dump_envelope(out, g)
+
+
+def dump_envelope(out, g):
+    """The envelope body's modes the cases above do not reach, at tiny shapes: every output bucket but 3, narrow
+    and wide workgroups, the list path and the forced walk, a coincident candidate, the slot buckets, the
+    streaming kernels (staged or not, the chain off, the gradient) and the fused launch."""
+    import torch
+
+    from dkg_amd.gp_state import DeviceGPState
+    from dkg_amd.model import ModelListGPState, SingleTaskGPState
+
+    dev, d = torch.device("cuda", 0), 3
+    rnd = lambda *shape: torch.rand(*shape, generator=g, dtype=torch.double)  # noqa: E731
+    kinds = (("matern", 2.5), ("rbf", 2.5), ("matern", 1.5), ("matern", 0.5), ("rbf", 2.5))
+
+    def models(m, n=20):
+        return ModelListGPState(*[
+            SingleTaskGPState(rnd(n - i, d), torch.randn(n - i, generator=g, dtype=torch.double), 0.3 + rnd(d),
+                              0.7 + 0.3 * i, 1e-2, 0.1 * i, kinds[i][0], kinds[i][1]) for i in range(m)])
+
+    def stats(key, plan, X):
+        for part, t in zip(("kg", "pairs", "hull_sizes"), plan.forward_stats(X)):
+            out[f"{key}/{part}"] = t.cpu()
+
+    def grads(key, plan, X):
+        for part, t in zip(("kg", "grad"), plan.forward_grad(X)):
+            out[f"{key}/grad_{part}"] = t.cpu()
+
+    X = rnd(5, d).to(dev)
+    for m in (1, 2, 4, 5):
+        st = DeviceGPState(models(m), rnd(50, d), dev)
+        for S in (3, 9):
+            w = 0.1 + rnd(S, m)
+            for walk in (False, True):
+                key = f"envelope/m{m}-S{S}{'-walk' if walk else ''}"
+                stats(key, st.plan(w, None, 5, force_walk=walk), X)
+                grads(key, st.plan(w, None, 5, grad=True, force_walk=walk), X)
+    # a candidate equal to a discretisation point: line 0 from its record
+    D = rnd(50, d)
+    st = DeviceGPState(models(2), D, dev)
+    Xc = torch.cat([X[:2].cpu(), D[7:8], X[2:4].cpu()]).to(dev)
+    stats("envelope/coincident", st.plan(0.1 + rnd(3, 2), None, 5), Xc)
+    grads("envelope/coincident", st.plan(0.1 + rnd(3, 2), None, 5, grad=True), Xc)
+    fused = st.plan(0.1 + rnd(3, 2), None, 5, fused=True)
+    assert fused.fused, "the library declined the fused launch at this shape"
+    out["envelope/fused/kg"] = fused.forward(X).cpu()
+    for N in (200, 600, 1500):  # slot buckets 8, 17, 33
+        sn = DeviceGPState(models(2), rnd(N, d), dev)
+        stats(f"envelope/N{N}", sn.plan(0.1 + rnd(3, 2), None, 3), X[:3])
+        grads(f"envelope/N{N}", sn.plan(0.1 + rnd(3, 2), None, 3, grad=True), X[:3])
+    for m in (1, 5):  # streaming, not staged-streaming
+        sn = DeviceGPState(models(m), rnd(2112, d), dev)
+        out[f"envelope/N2112-m{m}/kg"] = sn.plan(0.1 + rnd(3, m), None, 3).forward(X[:3]).cpu()
+    sn = DeviceGPState(models(3), rnd(2112, d), dev)
+    out["envelope/N2112-m3-no_chain/kg"] = sn.plan(0.1 + rnd(3, 3), None, 3, no_chain=True).forward(X[:3]).cpu()
+    sn = DeviceGPState(models(2), rnd(2112, d), dev)
+    grads("envelope/N2112-m2", sn.plan(0.1 + rnd(3, 2), None, 3, grad=True), X[:3])
 
 
 if len(sys.argv) > 2 and sys.argv[1] == "--dump":
